@@ -3,7 +3,20 @@
 (BASELINE.json metric; SURVEY 8d config 4 -- strong scaling 1/2/4/8 GPUs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 32768]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set-up, warm-up,
+the K timed steps, the JSON line (with the roofline figures that come from the
+timed launches' own HIP events and the committed PMC summaries).  --full adds
+what takes runs of its own: the CPU baselines below, the N > 1 parity solve,
+and the NS workload's separately timed normalizePressure.  --dump-outputs DIR
+writes what the timed steps left -- the fields a caller of the solve would
+download, and the iteration count and residual it returns -- as DIR/<name>.npy
+(float64; a field that does not fit the 64 MB budget is written as a fixed,
+seeded sample of its cells, with the sample's flat indices beside it).  The
+inputs are generated, not drawn, so two runs with the same arguments work on
+identical fields.
 
 A "step" is one red+black SOR iteration (one fused sweep launch, the
 reference's solveRB loop body, assignment-4/src/solver.c:197-234) over the
@@ -38,6 +51,7 @@ share one pass) is reported separately under iteration_equivalent.
 Warm-up: besides --warmup iterations, every kernel instantiation the timed
 region launches (T and the remainder steps % T) runs once before timing.
 
+The CPU baselines run with --full only.
 cpu_baseline: the reference's own solveRB (assignment-4/src/solver.c:179-238,
 compiled in place by oracle/Makefile into oracle/_ref/libref.so) on one host
 core, on the bench's own 32768^2 grid (the device's fields after the timed
@@ -58,7 +72,7 @@ launcher's RANK / LOCAL_RANK / WORLD_SIZE are used and WORLD_SIZE must equal
 --gpus (else exit 2); without a launcher, --gpus N > 1 spawns the N workers
 itself (this parent never touches the GPU: each worker selects its device
 before its first GPU call) and exits with their worst status.  Before timing,
-every N > 1 run solves a 2048^2 grid decomposed over the same ranks, gathers p
+every N > 1 run with --full solves a 2048^2 grid decomposed over the same ranks, gathers p
 on rank 0 and compares it bit for bit with a single-domain solve there
 (`parity`); `rccl_ranks` is the rank count of the bench grid's communicator
 as RCCL reports it (ncclCommCount).  --dry-run stops each worker before any
@@ -93,6 +107,33 @@ def runs_summary(vals):
     v = sorted(vals)
     med = v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2])
     return v[-1], med
+
+
+DUMP_BUDGET = 48 << 20  # bytes of field data per dump (64 MB in all, scalars and slack aside)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, fields, scalars):
+    """--dump-outputs: `fields` (name -> float64 array: what the timed steps
+    left on the device) and `scalars` (name -> number: what the timed call
+    returned) as path/<name>.npy, float64.  A field larger than its share of
+    DUMP_BUDGET is written as its values at a fixed sample of cells, the same
+    for every run of the same shape (seeded; sorted flat indices of the C-order
+    array, written beside it as <name>_index.npy -- exact in float64)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // max(len(fields), 1)
+    for name, a in fields.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.unique(rng.integers(0, a.size, share // 16))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    for name, v in scalars.items():
+        np.save(os.path.join(path, name + ".npy"), np.array([v], dtype=np.float64))
 
 
 def cpu_baseline(p, rhs, sweeps=3, runs=3):
@@ -280,9 +321,10 @@ def run_ns(args, world, rank, local_rank, dist, torch):
     g.reset_stats()
     barrier()
     t0 = time.perf_counter()
-    iters = 0
+    iters = last_it = 0
     for _ in range(args.steps):
-        iters += step()
+        last_it = step()
+        iters += last_it
     barrier()
     elapsed = time.perf_counter() - t0
     st = g.stats()
@@ -293,15 +335,25 @@ def run_ns(args, world, rank, local_rank, dist, torch):
     fg_ms = st["ns_ms"][0] / max(st["ns_calls"][0], 1)
     ad_ms = st["ns_ms"][1] / max(st["ns_calls"][1], 1)
     T_ns, passes_ns = st["iters_per_pass"], st["timed_passes"]
+    if args.dump_outputs:
+        # the state the timed steps left (gathered on rank 0: a collective)
+        fields = {name: g.gather(f) if world > 1 else g.download(f)
+                  for name, f in (("u", M.U), ("v", M.V), ("p", M.P))}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, fields,
+                         {"pressure_iterations": iters, "last_step_iterations": last_it})
+        del fields
     # normalizePressure runs every 100 steps (main.c:49): in the warm-up step
-    # 0, not in the timed steps -- timed here, after the timed region, on
-    # the field the steps left (3 calls)
-    g.reset_stats()
-    for _ in range(3):
-        g.call("normalize_pressure")
-    g.synchronize()
-    st2 = g.stats()
-    norm_ms = st2["ns_ms"][2] / max(st2["ns_calls"][2], 1)
+    # 0, not in the timed steps -- with --full timed here, after the timed
+    # region, on the field the steps left (3 calls)
+    norm_ms = 0.0
+    if args.full:
+        g.reset_stats()
+        for _ in range(3):
+            g.call("normalize_pressure")
+        g.synchronize()
+        st2 = g.stats()
+        norm_ms = st2["ns_ms"][2] / max(st2["ns_calls"][2], 1)
     if dist is not None:
         tt = torch.tensor([elapsed, solve_ms, pass_ms, fg_ms, ad_ms, norm_ms],
                           dtype=torch.float64, device="cuda")
@@ -375,13 +427,15 @@ def run_ns(args, world, rank, local_rank, dist, torch):
         "adapt_absmax_kernel": dict(roof(40.0 * lc, ad_ms, "adapt_absmax_kernel"),
                                     what="adaptUV + the next dt's max |u|, |v| (:438-455, "
                                          ":193-202)"),
-        "normalize_pressure": dict(roof(32.0 * lc, norm_ms, "normalize_pressure"),
-                                   what="normalizePressure (:204-217): absmax2 + exact_sum + "
-                                        "sub_mean, timed after the timed steps (3 calls)"),
     }
+    if args.full:
+        out["kernels"]["normalize_pressure"] = dict(
+            roof(32.0 * lc, norm_ms, "normalize_pressure"),
+            what="normalizePressure (:204-217): absmax2 + exact_sum + "
+                 "sub_mean, timed after the timed steps (3 calls)")
     if pm:
         out["roofline"]["traffic_source"] = pm.get("file")
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline_ns(g.loc.ni, g.loc.nj)
         except Exception as e:  # reported, never fatal for the GPU number
@@ -511,12 +565,21 @@ def run_ns3d(args, world, rank, local_rank, dist, torch):
     g.enable_timing(True)
     barrier()
     t0 = time.perf_counter()
-    iters = 0
+    iters = last_it = 0
     for _ in range(args.steps):
-        iters += step()
+        last_it = step()
+        iters += last_it
     barrier()
     elapsed = time.perf_counter() - t0
     solve_ms, solve_iters = g.solve_time()
+    if args.dump_outputs:
+        # the state the timed steps left (gathered on rank 0: a collective)
+        fields = {name: g.gather(f) if world > 1 else g.download(f)
+                  for name, f in (("u", M.U3), ("v", M.V3), ("w", M.W3), ("p", M.P3))}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, fields,
+                         {"pressure_iterations": iters, "last_step_iterations": last_it})
+        del fields
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -573,7 +636,7 @@ def run_ns3d(args, world, rank, local_rank, dist, torch):
                                           "k3_finish per iteration" if fused else
                                           "3D solve: k3_rb_pass x2 + k3_finish per iteration"),
                                "solve_ms_per_iteration": round(solve_ms / solve_iters, 5)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline3d(min(n, 128))
     g.close()
     return out
@@ -615,13 +678,13 @@ def run_poisson_local(args, N):
             g.synchronize()
             bar.wait()
             t0 = time.perf_counter()
-            it, _ = g.solve_rb(itermax=args.steps)
+            it, rs = g.solve_rb(itermax=args.steps)
             g.synchronize()
             bar.wait()
             el = time.perf_counter() - t0
             st = g.stats()
-            p = g.gather(M.P) if args.check else None
-            res[r] = dict(it=it, el=el, st=st, p=p, dims=tuple(g.loc.dims),
+            p = g.gather(M.P) if args.check or args.dump_outputs else None
+            res[r] = dict(it=it, el=el, st=st, p=p, res=rs, dims=tuple(g.loc.dims),
                           cells=g.loc.ni * g.loc.nj, T=st["iters_per_pass"])
             g.close()
         except BaseException as e:  # surfaced in the main thread
@@ -636,6 +699,9 @@ def run_poisson_local(args, N):
     if err:
         raise RuntimeError("local ranks failed: %s" % err)
     assert all(x["it"] == args.steps for x in res)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"p": res[0]["p"]},
+                     {"iterations": res[0]["it"], "residual": res[0]["res"]})
     elapsed = max(x["el"] for x in res)
     passes = max(max(x["st"]["timed_passes"], 1) for x in res)
     kern_ms = max(x["st"]["sweep_ms"] / max(x["st"]["timed_passes"], 1) for x in res)
@@ -813,7 +879,15 @@ def main():
     ap.add_argument("--steps", type=int, default=140)
     ap.add_argument("--warmup", type=int, default=7)
     ap.add_argument("--size", type=int, default=32768)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the CPU baselines, the N > 1 parity "
+                         "solve before timing, ns: normalizePressure timed after the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (fields, or a fixed "
+                         "seeded sample of a large one, and the solve's return values) as "
+                         "DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
     ap.add_argument("--tsteps", type=int, default=0,
                     help="iterations per kernel launch (0: library default)")
     ap.add_argument("--tb-variant", type=int, default=-1,
@@ -839,7 +913,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="stop before any GPU call; print this worker's rank assignment")
     ap.add_argument("--no-parity", action="store_true",
-                    help="N > 1: skip the pre-timing 2048^2 decomposed-vs-single parity solve")
+                    help="N > 1 with --full: skip the pre-timing 2048^2 decomposed-vs-single "
+                         "parity solve")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -914,7 +989,7 @@ def main():
     local_cells = g.loc.ni * g.loc.nj
     rccl_ranks = g.comm_ranks() if world > 1 else None
     parity = None
-    if world > 1 and not args.no_parity:
+    if world > 1 and args.full and not args.no_parity:
         parity = parity_check(world, rank, local_rank, dist)
 
     def barrier():
@@ -937,6 +1012,13 @@ def main():
     elapsed = time.perf_counter() - t0
     st = g.stats()
     assert it == args.steps, (it, args.steps)
+    if args.dump_outputs:
+        # what the timed solve returned and the p it left (gathered on rank 0:
+        # a collective)
+        hp = g.gather(M.P) if world > 1 else g.download(M.P)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"p": hp}, {"iterations": it, "residual": res})
+        del hp
 
     T = st["iters_per_pass"]
     # per launch (pass) of the sweep kernel, HIP events on the library's stream;
@@ -1076,7 +1158,7 @@ def main():
         out["rccl_ranks"] = rccl_ranks
         if parity is not None:
             out["parity"] = parity
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the bench's own grid (rank 0's block at N > 1): the fields the device
         # holds after the timed solve.  (A download of p exchanges its halo
         # first on a decomposed grid, a collective: every rank takes part.)

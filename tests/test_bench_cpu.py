@@ -56,6 +56,36 @@ def test_launcher_env_is_used():
     assert (d["rank"], d["local_rank"], d["world_size"], d["master_port"]) == (3, 3, 4, "29512")
 
 
+def test_full_and_dump_options_exist():
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", "unused",
+              "--dry-run"])
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1])["world_size"] == 1
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs' writer: a small field whole, a large one as the same
+    sample of cells every time, everything float64 and within 64 MB"""
+    import numpy as np
+
+    import bench
+
+    small = np.arange(12.0).reshape(3, 4)
+    big = np.arange(float(3000 * 3001)).reshape(3000, 3001)  # 72 MB
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big}, {"iterations": 7})
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["big.npy", "big_index.npy", "iterations.npy", "small.npy"]
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.array_equal(a["small.npy"], small) and a["iterations.npy"].tolist() == [7.0]
+    idx = a["big_index.npy"].astype(np.int64)
+    assert len(idx) > 1000000 and np.all(np.diff(idx) > 0) and idx[-1] < big.size
+    assert np.array_equal(a["big.npy"], big.reshape(-1)[idx])
+    for f, v in a.items():  # the same cells on every run
+        assert np.array_equal(v, np.load(tmp_path / "b" / f)), f
+
+
 @pytest.mark.parametrize("world,gpus", [("2", "4"), ("8", "1"), ("1", "8")])
 def test_world_size_mismatch_fails(world, gpus):
     r = _run(["--gpus", gpus, "--dry-run"], {"WORLD_SIZE": world, "RANK": "0", "LOCAL_RANK": "0"})

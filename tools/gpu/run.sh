@@ -7,12 +7,12 @@
 #   smoke   __graft_entry__.smoke()
 #   suite   python -m pytest tests -m gpu (the driver's GPU suite)
 #   tests=EXPR   the GPU tests selected by -k EXPR
-#   bench   bench.py --steps 20 --warmup 5 (the driver's N = 1 line, CPU baselines included)
-#   quick   bench.py --steps 20 --warmup 5 --no-cpu-baseline
+#   bench   bench.py --steps 20 --warmup 5 --full (the N = 1 line with the CPU baselines)
+#   quick   bench.py --steps 20 --warmup 5 (the plain run: no CPU baselines)
 #   trace   rocprofv3 --kernel-trace --stats of the quick bench
 #   pmc     rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ) of the quick bench
-#   ns      bench.py --workload ns (config 5, 16384^2), and its kernel trace + PMC
-#   ns3d    bench.py --workload ns3d (128^3)
+#   ns      bench.py --workload ns --full (config 5, 16384^2), and its kernel trace + PMC
+#   ns3d    bench.py --workload ns3d --full (128^3)
 #   proxy   one-GPU proxies of the decomposed ranks (needs lib_proxy, the MISOR_PROXY build)
 #   micro   tools/micro/fp64_lat.bin (FP64 issue / latency microbenchmark)
 # Outputs: gpurun_out/TAG/...
@@ -52,10 +52,10 @@ for step in "$@"; do
             -k "${step#tests=}" > "$out/gpu_tests_k.log" 2>&1 || die "$step" gpu_tests_k.log
         tail -1 "$out/gpu_tests_k.log" ;;
     bench)
-        timeout -k 10 400 $B > "$out/bench.json" 2> "$out/bench.err" || die bench bench.err
+        timeout -k 10 400 $B --full > "$out/bench.json" 2> "$out/bench.err" || die bench bench.err
         python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('bench', d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['bound'])" "$out/bench.json" ;;
     quick)
-        timeout -k 10 200 $B --no-cpu-baseline > "$out/quick.json" 2> "$out/quick.err" || die quick quick.err
+        timeout -k 10 200 $B > "$out/quick.json" 2> "$out/quick.err" || die quick quick.err
         python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('quick', d['ms_per_step'], d['roofline']['kernel_ms'])" "$out/quick.json" ;;
     trace)
         timeout -s KILL 200 rocprofv3 --kernel-trace --stats -d "$out/trace" -o trace --output-format csv \
@@ -63,13 +63,13 @@ for step in "$@"; do
     pmc)
         pmc_passes bench $B --no-cpu-baseline || die pmc bench_sq.log ;;
     ns)
-        timeout -k 10 300 $NS > "$out/ns.json" 2> "$out/ns.err" || die ns ns.err
+        timeout -k 10 300 $NS --full > "$out/ns.json" 2> "$out/ns.err" || die ns ns.err
         python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('NS', d['ms_per_step'], d['solve_kernel_ms_per_step'], d['other_ms_per_step'])" "$out/ns.json"
         timeout -s KILL 200 rocprofv3 --kernel-trace --stats -d "$out/ns_trace" -o trace --output-format csv \
-            -- $NS --no-cpu-baseline > "$out/ns_trace.log" 2>&1 || die ns-trace ns_trace.log
-        pmc_passes ns $NS --no-cpu-baseline || die ns-pmc ns_sq.log ;;
+            -- $NS --full --no-cpu-baseline > "$out/ns_trace.log" 2>&1 || die ns-trace ns_trace.log
+        pmc_passes ns $NS --full --no-cpu-baseline || die ns-pmc ns_sq.log ;;
     ns3d)
-        timeout -k 10 300 python bench.py --workload ns3d --steps 5 --warmup 2 > "$out/ns3d.json" \
+        timeout -k 10 300 python bench.py --workload ns3d --steps 5 --warmup 2 --full > "$out/ns3d.json" \
             2> "$out/ns3d.err" || die ns3d ns3d.err ;;
     proxy)
         P="python tools/scale_proxy.py --sweeps 20 --rows 0 --tsteps 10 --variants 13 --rounds 5"
