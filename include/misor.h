@@ -262,15 +262,26 @@ enum {
                                     * (order-independent) sum of r^2, so the iteration count
                                     * and res do not depend on the partition.  Default 10;
                                     * >= 300: off (set by tests to force the path: -30) */,
-    MISOR_TUNE_RES_LITE = 15       /* single rank, 10-iteration split-ring passes: 1
-                                    * (default) = the steady chunks count the residual of
-                                    * a pass's iterations but its last on one row in S, a
-                                    * lower bound that the loop test accepts only where it
-                                    * proves the loop goes on (not converged, not near the
-                                    * threshold); otherwise the pass is redone counting
-                                    * every cell and the solve continues so.  The iteration
-                                    * count, res and p are the same bits either way.
-                                    * 0 = every iteration counted in full */
+    MISOR_TUNE_RES_LITE = 15,      /* 10-iteration split-ring passes, one rank or
+                                    * decomposed: 1 (default) = the steady chunks count the
+                                    * residual of a pass's iterations but its last on one
+                                    * row in S, a lower bound that the loop test accepts
+                                    * only where it proves the loop goes on (not converged,
+                                    * not near the threshold; decomposed: the all-reduced
+                                    * sum of the ranks' bounds decides); otherwise the pass
+                                    * is redone counting every cell and the solve continues
+                                    * so.  The iteration count, res and p are the same bits
+                                    * either way.  0 = every iteration counted in full */
+    MISOR_TUNE_EDGE_STEAL = 16     /* whole passes of the split ring (TB variant 13): 1
+                                    * (default) = the edge kernel's workgroups, their own
+                                    * list done, steal runs of 4 or more blocks from the
+                                    * main kernel's list while it runs; 0 = they never
+                                    * steal; 2 (diagnostics) = the main kernel is launched
+                                    * in stream order behind the edge kernel, which so
+                                    * splits every main segment down to fewer than 4
+                                    * unclaimed blocks before the main kernel starts (the
+                                    * steals forced, for tests).  p and res are the same
+                                    * bits for every value */
 };
 int misor_set_tuning(misor_grid* g, int key, int value);
 int misor_get_tuning(const misor_grid* g, int key, int* value);
@@ -278,7 +289,9 @@ int misor_get_tuning(const misor_grid* g, int key, int* value);
 /* diagnostics: with MISOR_CHAIN_TRACE=1 in the environment when the grid is
  * configured, the per-block timeline of the last chained pass (3 words per
  * block L = by * nbx + bx: start and end on the 100 MHz wall clock, workgroup
- * | 1 << 32 for the first block of a run); *n = words available */
+ * | 1 << 32 for the first block of a run | 1 << 33 for a block run by the
+ * edge kernel, whose workgroups are numbered from 0 like the main kernel's);
+ * *n = words available */
 int misor_chain_trace(misor_grid* g, unsigned long long* out, long long cap, long long* n);
 
 int misor_enable_timing(misor_grid* g, int on);

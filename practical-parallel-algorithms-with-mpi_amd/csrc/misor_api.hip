@@ -764,6 +764,10 @@ int misor_set_tuning(misor_grid* g, int key, int value) {
         if (value != 0 && value != 1) return fail(MISOR_EINVAL, "RES_LITE is 0 or 1");
         g->res_lite = value != 0;
         return MISOR_OK;
+    case MISOR_TUNE_EDGE_STEAL:
+        if (value < 0 || value > 2) return fail(MISOR_EINVAL, "EDGE_STEAL is 0, 1 or 2");
+        g->edge_steal = value;
+        return MISOR_OK;
     default: return fail(MISOR_EINVAL, "unknown tuning key %d", key);
     }
 }
@@ -783,6 +787,7 @@ int misor_get_tuning(const misor_grid* g, int key, int* value) {
     case MISOR_TUNE_TB_CHAIN: *value = chain_on(g, g->tp.variant); return MISOR_OK;
     case MISOR_TUNE_NEAR_BAND: *value = g->near_exp; return MISOR_OK;
     case MISOR_TUNE_RES_LITE: *value = g->res_lite; return MISOR_OK;
+    case MISOR_TUNE_EDGE_STEAL: *value = g->edge_steal; return MISOR_OK;
     case MISOR_TUNE_NS_FUSE: *value = g->ns_fuse; return MISOR_OK;
     case MISOR_TUNE_FINISH2: *value = g->finish2; return MISOR_OK;
     case MISOR_TUNE_TB_RESERVE: *value = g->tb_reserve; return MISOR_OK;

@@ -121,8 +121,9 @@ struct misor_grid {
     int near_exp = 10;
     double* rsq = nullptr;  // exact_tail: r^2 per cell (allocated on first use)
     bool small_solve = true;  // whole-solve LDS kernel when p fits (single rank)
-    // MISOR_TUNE_RES_LITE: single-rank 10-iteration split-ring passes count the
-    // residual of their inner iterations on one row in S (misor_solve.hip)
+    // MISOR_TUNE_RES_LITE: 10-iteration split-ring passes (one rank or
+    // decomposed) count the residual of their inner iterations on one row in S
+    // (misor_solve.hip)
     bool res_lite = true;
     bool lite_block = false;  // the rest of this solve counts in full (a lower bound missed)
 
@@ -160,6 +161,10 @@ struct misor_grid {
     long long tb_work_bytes[4] = {0, 0, 0, 0};
     hipStream_t xstream[2] = {nullptr, nullptr};  // edge kernels (parts 0-1 / 2)
     hipEvent_t ev_fork[2] = {}, ev_join[2] = {};
+    // MISOR_TUNE_EDGE_STEAL, whole split-ring passes: 1 the edge kernel's
+    // workgroups steal from the main list, 0 never, 2 (diagnostics) the main
+    // kernel launched behind the edge kernel (misor_solve.hip)
+    int edge_steal = 1;
     // MISOR_CHAIN_TRACE=1: per-block timeline of the last chained pass (diagnostics)
     unsigned long long* chain_trace = nullptr;
     long long chain_trace_blocks = 0, chain_trace_last = 0;
@@ -245,6 +250,7 @@ MISOR_HIDDEN int effective_tsteps(const misor_grid* g);
 MISOR_HIDDEN int ensure_partials(misor_grid* g, int n);
 MISOR_HIDDEN int pick_rows_per_block(int ni, int nj, int waves);
 MISOR_HIDDEN void tb_geometry(const misor_grid* g, int T, SweepParams& tp);
+MISOR_HIDDEN int tb_halo_depth(int T, int variant);
 MISOR_HIDDEN int tb_parts(const SweepParams& tp);
 
 // misor_solve.hip

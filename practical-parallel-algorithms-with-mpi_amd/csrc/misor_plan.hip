@@ -49,15 +49,27 @@ int configure_sweep(misor_grid* g, int variant, int rows, int remap) {
     return ensure_partials(g, g->nparts);
 }
 
+// halo depth a decomposed pass of T iterations of `variant` exchanges: 2T, one
+// row more for the skewed split ring (its leading stages run one row ahead of
+// the trailing ones; the top rows of their residual windows at a neighbour
+// above read row nj + 2T + 1)
+int tb_halo_depth(int T, int variant) {
+    return 2 * T + (T >= 2 && variant == kHrTbVariant ? 1 : 0);
+}
+
 // T that a multi-block solve uses: the requested one, limited so that the
-// 2T-deep halo of a decomposed run fits inside the smallest neighbour block
+// halo of a decomposed run (tb_halo_depth) fits inside the smallest neighbour
+// block.  The skewed split ring never runs with a 2T-deep halo: on a block
+// whose smallest side is exactly 2T it runs T - 1 iterations a pass
+// (misor_stats.iters_per_pass reports the T in effect).
 int effective_tsteps(const misor_grid* g) {
     int T = g->tsteps;
     if (T < 1) T = 1;
     if (T > kMaxT) T = kMaxT;
     if (g->dist) {
         const int mi = g->desc.imax / g->loc.dims[0], mj = g->desc.jmax / g->loc.dims[1];
-        while (T > 1 && (2 * T > mi || 2 * T > mj || 2 * T > g->max_depth)) --T;
+        const int cap = std::min(std::min(mi, mj), g->max_depth);
+        while (T > 1 && tb_halo_depth(T, g->tp.variant) > cap) --T;
     }
     return T;
 }

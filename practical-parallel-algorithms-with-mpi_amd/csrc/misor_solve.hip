@@ -261,7 +261,9 @@ int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters,
     // of more than 8 iterations takes it.
     const int todo0 = itermax - it0;
     const bool all = g->short_all || (g->short_all_lite && g->res_lite);
-    const bool shortp = g->short_plan && effective_tsteps(g) == kDefaultTsteps &&
+    // (decomposed: only where the smallest block holds the split ring's halo)
+    const bool short_fits = !g->dist || tb_halo_depth(kShortT, kShortTbVariant) <= g->max_depth;
+    const bool shortp = g->short_plan && short_fits && effective_tsteps(g) == kDefaultTsteps &&
                         (all ? todo0 > kDefaultTsteps
                                       : 7LL * ((todo0 + kShortT - 1) / kShortT) <
                                             5LL * ((todo0 + kDefaultTsteps - 1) / kDefaultTsteps));
@@ -275,10 +277,14 @@ int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters,
     g->comm_timing = g->timing && g->dist;
     g->cev_used[0] = g->cev_used[1] = 0;
     // halo of src each pass needs: 2T, one row more for the skewed split ring
-    // (its leading stages run one row ahead of the trailing ones; the top rows
-    // of their residual windows at a neighbour above read row nj + 2T + 1)
-    const int depth = 2 * T + (T >= 2 && tpl.variant == kHrTbVariant && 2 * T < g->max_depth);
-    // Residual lower bounds (MISOR_TUNE_RES_LITE): on one rank, a
+    // (tb_halo_depth).  effective_tsteps and short_fits keep it within the
+    // halo plans: with a 2T-deep halo the split ring's leading stages would
+    // count a stale row into their residuals
+    const int depth = tb_halo_depth(T, tpl.variant);
+    if (g->dist && depth > g->max_depth)
+        return fail(MISOR_ESTATE, "halo depth %d of a %d-iteration pass exceeds %d", depth, T,
+                    g->max_depth);
+    // Residual lower bounds (MISOR_TUNE_RES_LITE), one rank or decomposed: a
     // kShortT-iteration split-ring pass counts r^2 of its iterations but the
     // last on one row in S of its steady chunks (sor_tbh.h hrs_step LITE), one
     // FP64 FMA per update fewer on a VALU-bound pass.  Each such sum is a lower
@@ -348,9 +354,21 @@ int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters,
                 tm.reserve += pl->edge.blocks > 0 ? eg : 0;
                 const bool has_e = pl->edge.blocks > 0, has_m = pl->main.blocks > 0;
                 // (no edge list: the main kernel alone, on s)
-                const bool fork = has_e && has_m;
+                const bool both = has_e && has_m;
+                // MISOR_TUNE_EDGE_STEAL (whole split-ring passes): 0 = the edge
+                // kernel never takes from the main list; 2 (diagnostics) = the
+                // main kernel in stream order behind the edge kernel, whose
+                // workgroups, their list done, find every main segment whole
+                // and split each down to fewer than 4 unclaimed blocks.  The
+                // edge kernel never waits for the main one (chain_acquire's
+                // steal loop ends when no segment has 4 unclaimed blocks; the
+                // main kernel's tickets are not its to take), so it ends
+                // whether or not the main kernel has started.
+                const int steal =
+                    !(both && part == 0) ? 0 : tp.variant == kHrTbVariant ? g->edge_steal : 1;
+                const bool fork = both && steal != 2;
                 hipStream_t ms = fork ? g->xstream[k] : s;
-                if (fork) {
+                if (both) {
                     // A whole pass: the edge kernel's workgroups go on to steal
                     // from the main list once the edge list is done (its 2.5x
                     // block cost is an estimate: its kernel ended ~2.5 ms before
@@ -360,15 +378,17 @@ int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters,
                     // there the edge slots, once free, are part 2's
                     // (profiles/r06_edge_steal_ab.txt: the 8-GPU rank's loop 3%
                     // slower with them stealing)
-                    if (part == 0) {
+                    if (steal) {
                         launch_chain_init(s, g->tb_work[k], pl->main.tmpl, pl->main.nseg0,
                                           tm.seg_cap);
                         tm.no_init = 1;
                         te.alt_work = g->tb_work[k];
                         te.alt_nseg0 = pl->main.nseg0;
                     }
-                    HIPCHK(hipEventRecord(g->ev_fork[k], s));
-                    HIPCHK(hipStreamWaitEvent(g->xstream[k], g->ev_fork[k], 0));
+                    if (fork) {
+                        HIPCHK(hipEventRecord(g->ev_fork[k], s));
+                        HIPCHK(hipStreamWaitEvent(g->xstream[k], g->ev_fork[k], 0));
+                    }
                 }
                 if (has_e)
                     launch_tb(s, Tp, te, src, dst, rhs, partials, g->st, force, g->tb_work[2 + k]);

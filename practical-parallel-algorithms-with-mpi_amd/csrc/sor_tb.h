@@ -1059,7 +1059,9 @@ __device__ __forceinline__ int chain_block_end(const SweepParams& prm, Acc (&acc
         unsigned long long* tr = prm.trace + 3ll * L;
         tr[0] = *reinterpret_cast<volatile unsigned long long*>(sh + 4);
         tr[1] = now;
-        tr[2] = blockIdx.x | (sh[6] ? 1ull << 32 : 0ull);
+        // (bit 33: the edge kernel's launch -- both kernels number their
+        // workgroups from 0, and its workgroups also run stolen main-list blocks)
+        tr[2] = blockIdx.x | (sh[6] ? 1ull << 32 : 0ull) | (prm.chain_edge ? 1ull << 33 : 0ull);
         *reinterpret_cast<volatile unsigned long long*>(sh + 4) = now;
         sh[6] = 0;
     }

@@ -26,7 +26,8 @@ SOLVE_RB, SOLVE_RBA = 0, 1
 LEX_A4, LEX_SEQ = 0, 1
 (TUNE_SWEEP_VARIANT, TUNE_ROWS_PER_BLOCK, TUNE_XCD_REMAP, TUNE_SMALL_SOLVE, TUNE_OVERLAP,
  TUNE_TSTEPS, TUNE_TB_VARIANT, TUNE_TB_ROWS, TUNE_TB_PERSISTENT, TUNE_NS_FUSE,
- TUNE_FINISH2, TUNE_TB_RESERVE, TUNE_TB_CHAIN, TUNE_NEAR_BAND, TUNE_RES_LITE) = range(1, 16)
+ TUNE_FINISH2, TUNE_TB_RESERVE, TUNE_TB_CHAIN, TUNE_NEAR_BAND, TUNE_RES_LITE,
+ TUNE_EDGE_STEAL) = range(1, 17)
 COMM_ID_BYTES = 128
 # 3D field ids (misor3_*)
 P3, RHS3, U3, V3, W3, F3, G3, H3 = range(8)
@@ -351,7 +352,9 @@ class Grid:
     def chain_trace(self):
         """per-block timeline of the last chained pass (MISOR_CHAIN_TRACE=1 at
         configure time): array (blocks, 3) of start, end (100 MHz clock) and
-        workgroup | 1 << 32 for a run's first block; None if not traced"""
+        workgroup | 1 << 32 for a run's first block | 1 << 33 for a block run by
+        the edge kernel (both kernels number their workgroups from 0); row
+        L = by * nbx + bx; None if not traced"""
         import numpy as np
         n = C.c_longlong(0)
         _check(lib().misor_chain_trace(self.h, None, 0, C.byref(n)))

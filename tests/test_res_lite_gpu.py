@@ -13,6 +13,7 @@ bounds off bit for bit, res included: when the bounds decide every iteration,
 when one misses near convergence, and when one misses at once (a near band
 that takes in every residual).
 """
+import functools
 import threading
 
 import numpy as np
@@ -121,17 +122,22 @@ def test_bound_misses_at_once(converging):
     assert st["lite_misses"] == 1
 
 
-def ranks(world, p0, rhs, dx, dy, eps, itermax, lite, band=None, T=10, variant=13):
+def ranks(world, p0, rhs, dx, dy, eps, itermax, lite, band=None, T=10, variant=13,
+          ni=NI, nj=NJ, dims=(0, 0), stats=None):
     """`world` in-process ranks (LOCAL transport, the pipelined decomposed loop
-    with its 2T-deep exchanges); the owned blocks assembled into one field"""
-    cid = ("LOCAL:lite%d_%d_%s_%g_%d_%d_%d" % (world, lite, band, eps, itermax, T,
-                                               variant)).encode()
+    with its 2T-deep exchanges); the owned blocks assembled into one field.
+    dims: the process grid (0, 0: the library's balanced one); stats: a dict
+    that receives rank 0's misor_stats"""
+    cid = "LOCAL:lite%d_%d_%s_%g_%d_%d_%d" % (world, lite, band, eps, itermax, T, variant)
+    if (ni, nj, tuple(dims)) != (NI, NJ, (0, 0)):
+        cid += "_%dx%d_%dx%d" % (ni, nj, dims[0], dims[1])
+    cid = cid.encode()
     outs, errs = [None] * world, []
 
     def body(r):
         try:
-            with M.Grid(NI, NJ, dx, dy, 1.9, eps, itermax, device=0, nranks=world, rank=r,
-                        comm_id=cid) as g:
+            with M.Grid(ni, nj, dx, dy, 1.9, eps, itermax, device=0, nranks=world, rank=r,
+                        dims=dims, comm_id=cid) as g:
                 g.set_tuning(M.TUNE_TB_VARIANT, variant)
                 g.set_tuning(M.TUNE_TSTEPS, T)
                 g.set_tuning(M.TUNE_RES_LITE, lite)
@@ -143,7 +149,10 @@ def ranks(world, p0, rhs, dx, dy, eps, itermax, lite, band=None, T=10, variant=1
                 g.upload(M.RHS, np.ascontiguousarray(
                     rhs[loc.joff:loc.joff + loc.nj + 2, loc.ioff:loc.ioff + loc.ni + 2]))
                 it, res = g.solve_rb()
-                outs[r] = (loc, g.download(M.P), it, res, g.stats()["lite_misses"])
+                st = g.stats()
+                outs[r] = (loc, g.download(M.P), it, res, st["lite_misses"])
+                if stats is not None and r == 0:
+                    stats.update(st)
         except BaseException as e:
             errs.append((r, repr(e)))
 
@@ -228,6 +237,82 @@ def test_decomposed_leading_stage_near_eps():
         got, it, r, _ = ranks(4, p0, rhs, dx, dy, eps, 100000, 0, band=400)
         assert it == k, (k, it)
         assert abs(r - res[k]) <= 1e-12 * res[k]
+
+
+# The smallest decomposed block: two ranks whose local side across the split is
+# exactly 2T for the requested T.  The skewed split ring exchanges a 2T + 1-deep
+# halo, which such a block cannot hold, so the library runs T - 1 iterations a
+# pass there (misor_plan.hip effective_tsteps); with a 2T-deep halo its leading
+# stages would count a stale row into their residuals.
+SMALLEST = [(T, dims) for T in (3, 4, 10) for dims in ((1, 2), (2, 1))]
+# ten consecutive iterations from the second pass on: every stage of a pass of
+# any T <= 10 (T = 10: stages 2 .. 10, 1; T = 9: 3 .. 9, 1 .. 3)
+K0 = 12
+
+
+def smallest_shape(T, dims):
+    return (600, 4 * T) if dims == (1, 2) else (4 * T, 600)
+
+
+@functools.lru_cache(maxsize=None)
+def smallest_sequence(ni, nj):
+    """the restatement's residual after each of 21 iterations from
+    p = N(0, 1) * 2^-30, rhs = 0 (one iteration at a time), and its field after
+    each of the ten iterations K0 .. K0 + 9 (none of them changed afterwards)"""
+    rng = np.random.default_rng(7)
+    p0 = rng.standard_normal((nj + 2, ni + 2)) * 2.0 ** -30
+    rhs = np.zeros_like(p0)
+    q, res, field = p0.copy(), {}, {}
+    for k in range(1, K0 + 10):
+        res[k] = orc.solve_rb(q, rhs, 1.0 / ni, 1.0 / nj, 1.9, 1e-300, 1)[1]
+        if k >= K0:
+            field[k] = q.copy()
+    for a in (p0, rhs, *field.values()):
+        a.setflags(write=False)
+    return p0, rhs, res, field
+
+
+@pytest.mark.parametrize("T,dims", SMALLEST)
+def test_smallest_block_every_stage(T, dims):
+    """eps^2 = res[k] (1 + 5e-7) for ten consecutive k, each below every
+    earlier residual: the solve stops at k exactly, with the restatement's p
+    bit for bit and its res to 1e-12, whichever stage of a pass k is.  The
+    library lowers T to T - 1 (2T + 1 <= the block's side)."""
+    ni, nj = smallest_shape(T, dims)
+    p0, rhs, res, field = smallest_sequence(ni, nj)
+    ks = list(range(K0, K0 + 10))
+    for k in ks:  # (seed 7 on the CPU: the residuals fall ~18% an iteration)
+        assert res[k] * (1 + 5e-7) < min(res[j] for j in range(1, k)), k
+    for k in ks:
+        eps = (res[k] * (1 + 5e-7)) ** 0.5
+        st = {}
+        got, it, r, _ = ranks(2, p0, rhs, 1.0 / ni, 1.0 / nj, eps, 100000, 0, band=400, T=T,
+                              ni=ni, nj=nj, dims=dims, stats=st)
+        print("T %d dims %s k %d: it %d res %.17g want %.17g rel %.3g per pass %d" % (
+            T, dims, k, it, r, res[k], abs(r - res[k]) / res[k], st["iters_per_pass"]))
+        assert st["iters_per_pass"] == T - 1 and st["tb_variant"] == 13
+        assert it == k, (k, it)
+        assert np.array_equal(got, field[k]), k
+        assert abs(r - res[k]) <= 1e-12 * res[k], (k, r, res[k])
+
+
+@pytest.mark.parametrize("T,dims", SMALLEST)
+def test_smallest_block_fixed_iterations(T, dims):
+    """2T + 1 iterations of random fields on the same blocks: p bit for bit"""
+    ni, nj = smallest_shape(T, dims)
+    rng = np.random.default_rng(100 * T + dims[0])
+    p = rng.standard_normal((nj + 2, ni + 2))
+    rhs = rng.standard_normal((nj + 2, ni + 2))
+    dx, dy, k = 1.0 / ni, 1.0 / nj, 2 * T + 1
+    want = p.copy()
+    it_w, res_w = orc.solve_rb(want, rhs, dx, dy, 1.9, 1e-300, k)
+    st = {}
+    got, it, r, _ = ranks(2, p, rhs, dx, dy, 1e-300, k, 0, band=400, T=T, ni=ni, nj=nj,
+                          dims=dims, stats=st)
+    assert st["iters_per_pass"] == T - 1
+    assert it == it_w == k
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+    assert abs(r - res_w) <= 1e-12 * res_w
 
 
 def test_bad_setting_refused():

@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--T", type=int, default=8)
     ap.add_argument("--variant", type=int, default=-1, help="TB variant (13: the split ring)")
     ap.add_argument("--rows", type=int, default=0)
+    ap.add_argument("--edge-steal", type=int, default=1,
+                    help="MISOR_TUNE_EDGE_STEAL (split ring: 0 never, 2 forced)")
     ap.add_argument("--passes", type=int, default=3, help="traced solves (last one kept)")
     ap.add_argument("--per-solve", type=int, default=1, help="passes per solve (the last traced)")
     a = ap.parse_args()
@@ -40,7 +42,8 @@ def main():
     g.set_tuning(M.TUNE_TSTEPS, a.T)
     if a.rows:
         g.set_tuning(M.TUNE_TB_ROWS, a.rows)
-    H = g.get_tuning(M.TUNE_TB_ROWS)
+    g.set_tuning(M.TUNE_EDGE_STEAL, a.edge_steal)
+    H =g.get_tuning(M.TUNE_TB_ROWS)
     spans = []
     g.enable_timing(True)
     for _ in range(a.passes):
@@ -55,8 +58,12 @@ def main():
     g.close()
     st = tr[:, 0].astype(np.int64)
     en = tr[:, 1].astype(np.int64)
-    wg = (tr[:, 2] & 0xffffffff).astype(np.int64)
-    first = (tr[:, 2] >> np.uint64(32)).astype(bool)
+    # word 2: workgroup | 1 << 32 (a run's first block) | 1 << 33 (run by the
+    # edge kernel, which numbers its workgroups from 0 like the main one: its
+    # workgroups get ids of their own here)
+    by_edge = ((tr[:, 2] >> np.uint64(33)) & np.uint64(1)).astype(bool)
+    wg = (tr[:, 2] & np.uint64(0xffffffff)).astype(np.int64) + (by_edge.astype(np.int64) << 32)
+    first = ((tr[:, 2] >> np.uint64(32)) & np.uint64(1)).astype(bool)
     t0 = st.min()
     st, en = st - t0, en - t0
     span = en.max()
@@ -108,6 +115,9 @@ def main():
                   for q in range(4) if (pos == q).any()) +
         ", 4+: %.1f (p90 %.1f)" % (np.median(dur[pos >= 4]), np.percentile(dur[pos >= 4], 90)),
         np.median(dur[edge]), np.median(dur[~edge])))
+    print("blocks run by the edge kernel: %d, %d of them in the other columns (stolen from the "
+          "main list: %.1f%% of its blocks)" % (by_edge.sum(), (by_edge & ~edge).sum(),
+                                               100.0 * (by_edge & ~edge).sum() / max((~edge).sum(), 1)))
     # durations over time (when in the pass a block ran)
     tb = np.linspace(0, span, 11)
     print("median block us per 10%% of the span (non-edge, chained): %s" % " ".join(
