@@ -59,30 +59,30 @@ constexpr int kNumSweepVariants = 15;
 constexpr int kDefaultSweepVariant = 7;  // 8 strips, 2 rows ahead, nt stores (tools/tune_sweep.py)
 int sweep_waves(int variant);
 
-// temporally blocked sweep (sor_tb.hip): strips per workgroup, rows in flight
-// (x-neighbour shifts through ds_bpermute instead of DPP -- the kernel's BP
-// template flag -- measured 5% slower: profiles/r02_tune_bperm.txt)
+// temporally blocked sweep (sor_tb.hip): the built variants by their public
+// number (id): strips per workgroup, rows in flight
+// (x-neighbour shifts through ds_bpermute instead of DPP measured 5% slower:
+// profiles/r02_tune_bperm.txt)
 // 128-column strips (2 columns per lane), 2 waves per SIMD.
 // skew: the split-ring march in two independent stage chains per step (sor_tbh.h
 // hrs_step); hr: the split rhs ring, registers + LDS (sor_tbh.h)
-// max_t = 0: retired -- measured slower and no longer built (DESIGN.md section 4:
+// The other numbers below kNumTbVariants are retired -- measured slower and no
+// longer built (DESIGN.md section 4:
 // 1 / 3 eight / one strips per workgroup, 4 three rows in flight, 5 four
 // columns per lane at one wave per SIMD, 6-8 strips exchanging edge columns
 // through LDS, 9 the skewed register-ring march, 10/11 an LDS row queue, 12 the
-// unskewed split ring); configuring one fails.  The register-ring kernels run
-// T <= kMaxT2 (above that their rhs ring spills); the split ring (13) runs T up
-// to kMaxT.
+// unskewed split ring); configuring one fails (tb_max_t = 0).  The register-ring
+// kernels run T <= kMaxT2 (above that their rhs ring spills); the split ring
+// (13) runs T up to kMaxT.
 constexpr int kMaxT2 = 8;
 struct TbVariant {
-    int waves, ahead, max_t, skew, hr;
+    int id, waves, ahead, max_t, skew, hr;
 };
 constexpr TbVariant kTbVariants[] = {
-    {4, 2, kMaxT2}, {4, 2, 0}, {2, 2, kMaxT2}, {4, 2, 0}, {4, 2, 0}, {4, 2, 0}, {4, 2, 0},
-    {4, 2, 0},      {4, 2, 0}, {4, 2, 0},      {4, 2, 0}, {4, 2, 0}, {4, 2, 0},
-    {4, 2, kMaxT, 1, 1}};
+    {0, 4, 2, kMaxT2, 0, 0}, {2, 2, 2, kMaxT2, 0, 0}, {13, 4, 2, kMaxT, 1, 1}};
 constexpr int kNumTbVariants = 14;
 constexpr int kHrTbVariant = 13;   // the skewed split ring (T = 1 unskewed)
-// the short plan of capped solves (misor_api.hip solve_rb_from)
+// the short plan of capped solves (misor_solve.hip solve_rb_from)
 constexpr int kShortTbVariant = kHrTbVariant;
 constexpr int kShortT = 10;
 constexpr long long kShortDistCells = 1LL << 28;  // decomposed: local blocks at least this big
@@ -95,7 +95,7 @@ constexpr int kDefaultTsteps = 8;
 constexpr int kSmallBlockTsteps = 7;
 constexpr long long kTsteps8Cells = 1LL << 28;
 constexpr int kDefaultTbVariant = 0;   // 4 strips, 2 rows in flight
-// block heights tried, tallest first (misor_api.hip pick_tb_rows)
+// block heights tried, tallest first (misor_plan.hip pick_tb_rows)
 constexpr int kTbRowLadder[] = {576, 384, 288, 192};
 constexpr int kTbRowLadderLen = 4;
 constexpr int kTbSmallRows = 32;       // short block rows the work order takes last ...
@@ -136,7 +136,7 @@ struct DevState {
     int done;      // 1 once (res >= eps^2 && it < itermax) is false
     int itermax;   // cap of the current solve call
     int near;      // 1: stopped before iteration it+1, whose res fell within nband of
-                   // eps^2 (misor_api.hip exact_tail recomputes from there)
+                   // eps^2 (misor_solve.hip exact_tail recomputes from there)
     int lite_miss; // 1: stopped before iteration it+1, whose residual lower bound (a
                    // lite pass, SweepParams::lite) did not prove the loop goes on
     double res;    // residual of the last iteration

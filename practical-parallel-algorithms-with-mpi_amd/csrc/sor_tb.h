@@ -1,8 +1,6 @@
 // sor_tb.h -- device code of the temporally blocked sweep (included by the
-// per-T instantiation units sor_tb_inst.hip; launchers in sor_tb.hip).
-#pragma once
-// sor_tb.hip -- temporally blocked red-black SOR for gfx950: T complete
-// solveRB iterations (assignment-4/src/solver.c:197-229, T = 2..kMaxT) per
+// per-T instantiation units sor_tb_inst.hip; launchers in sor_tb.hip):
+// temporally blocked red-black SOR for gfx950, T complete solveRB iterations (assignment-4/src/solver.c:197-229, T = 2..kMaxT) per
 // pass over HBM.
 //
 // The single-iteration sweep (sor_kernels.hip) already moves the algorithmic
@@ -72,10 +70,11 @@
 // workgroup per stage in a fixed order; the finish kernel decides iteration by
 // iteration exactly like the single-sweep path.  If convergence (or itermax)
 // is reached at stage t < T, the host recomputes that pass with T' = t from
-// the untouched source buffer (misor_api.hip), so the returned field is the
+// the untouched source buffer (misor_solve.hip), so the returned field is the
 // one after exactly `it` iterations.
 //
 // Bit-exactness: same expression order as the reference, -ffp-contract=off.
+#pragma once
 
 #include <algorithm>
 #include <utility>
@@ -101,13 +100,6 @@ __device__ __forceinline__ double from_right(double v) {
                             __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true));
 }
 
-// the same shifts through the LDS crossbar (ds_bpermute: an LDS-pipe
-// instruction, so the shift costs no VALU issue slot); addr = source lane * 4
-__device__ __forceinline__ double bperm(double v, int addr) {
-    return __hiloint2double(__builtin_amdgcn_ds_bpermute(addr, __double2hiint(v)),
-                            __builtin_amdgcn_ds_bpermute(addr, __double2loint(v)));
-}
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -126,7 +118,7 @@ __device__ __forceinline__ double m2c(double a, double c) { return __builtin_fma
 // (a subnormal a + b is exact too) and rhs minus that exact product is one
 // fma -- the same bits with 2 of the 11 FP64 instructions of an update fewer.
 // Holds while |a| k and |b| k stay below DBL_MAX (|p| < ~1e298 at k = 2^30);
-// the host enables it only for such a spacing (misor_api.hip configure_tb).
+// the host enables it only for such a spacing (misor_plan.hip configure_tb).
 template <bool P2>
 __device__ __forceinline__ double resid(double rhs, double a, double b, double idx2, double idy2) {
     if (P2) return __builtin_fma(-(a + b), idx2, rhs);
@@ -164,37 +156,11 @@ struct Lane {
     int wlo, whi;          // residual window reaches the physical bottom / top side
     int parity;
     int gb, gt, nj;
-    int bl, br;            // ds_bpermute addresses of lanes l-1 and l+1
     double idx2, idy2, coef;
 };
 
-// The per-lane residual accumulator.  MISOR_RES_BINNED (a cost experiment,
-// never the product build: tools/gpu_res_cost.sh) makes
-// the steady chunks deposit r^2 into two fixed bins instead (q1 = (M1 + x) -
-// M1, q2 = (M2 + (x - q1)) - M2, each added exactly): an order-independent
-// sum, i.e. what a partition-independent residual costs in the sweep.
-#ifdef MISOR_RES_BINNED
-struct TallyAcc {
-    double s1, s2;
-    __device__ TallyAcc& operator=(double v) {
-        s1 = v;
-        s2 = 0.0;
-        return *this;
-    }
-    __device__ operator double() const { return s1 + s2; }
-};
-__device__ __forceinline__ void tally_steady(TallyAcc& a, double r) {
-    constexpr double M1 = 0x1.8p+40, M2 = 0x1.8p-12;  // bins of 2^-12 and 2^-64
-    const double x = r * r;
-    const double q1 = (M1 + x) - M1;
-    const double q2 = (M2 + (x - q1)) - M2;
-    a.s1 += q1;
-    a.s2 += q2;
-}
-#else
-using TallyAcc = double;
+// the steady chunks' tally of a cell's r^2 into the lane's residual accumulator
 __device__ __forceinline__ void tally_steady(double& a, double r) { a = __builtin_fma(r, r, a); }
-#endif
 
 // How a step is compiled:
 //  kEdge    general: per-lane update / residual masks, ghost-row and
@@ -221,12 +187,9 @@ enum { kEdge = 0, kPre = 1, kSteady = 2, kRowEdge = 3, kSteadyEdge = 4 };
 // Stage 0 reads the ghost rows as they are in memory -- the state after the
 // previous pass, or whatever the caller uploaded, as the reference's first
 // iteration does.  Q: colour of the rows (0: column ia is red in row rin-1).
-template <int T, int Q, int MODE, bool BP = false, bool P2 = false, int SKH = 0, class Acc>
+template <int T, int Q, int MODE, bool P2 = false, int SKH = 0, class Acc>
 __device__ __forceinline__ d2 stage(const Lane& c, int t, bool fixrows, d2 In, int rin, d2& A,
                                     d2& M1, d2& M2, d2 Ra, d2 Rb, Acc& acc) {
-    // BP: x-neighbours through ds_bpermute instead of DPP (interior modes)
-    auto fl = [&](double v) { return BP ? bperm(v, c.bl) : from_left(v); };
-    auto fr = [&](double v) { return BP ? bperm(v, c.br) : from_right(v); };
     constexpr bool EDGE = MODE == kEdge || MODE == kSteadyEdge;  // lane masks
     constexpr bool ROWS = MODE == kEdge || MODE == kRowEdge;     // row tests, ghost rows
     if (ROWS && fixrows) {
@@ -269,13 +232,13 @@ __device__ __forceinline__ d2 stage(const Lane& c, int t, bool fixrows, d2 In, i
     d2 Mr = A;
     if (!ROWS || (rr >= c.lo_j && rr <= c.hi_j)) {
         if (Q == 0) {
-            const double Lf = fl(A.y);
+            const double Lf = from_left(A.y);
             const double cc = A.x;
             const double r = resid<P2>(Ra.x, m2c(A.y, cc) + Lf, m2c(In.x, cc) + M1.x, idx2, idy2);
             if (!EDGE || c.up_a) Mr.x = cc - coef * r;
             tally(r, rr, sh, c.own_a);
         } else {
-            const double Rf = fr(A.x);
+            const double Rf = from_right(A.x);
             const double cc = A.y;
             const double r = resid<P2>(Ra.y, m2c(Rf, cc) + A.x, m2c(In.y, cc) + M1.y, idx2, idy2);
             if (!EDGE || c.up_b) Mr.y = cc - coef * r;
@@ -287,13 +250,13 @@ __device__ __forceinline__ d2 stage(const Lane& c, int t, bool fixrows, d2 In, i
     d2 F = M1;
     if (!ROWS || (rb >= c.lo_j && rb <= c.hi_j)) {
         if (Q == 0) {
-            const double Ln = fl(M1.y);
+            const double Ln = from_left(M1.y);
             const double cc = M1.x;
             const double r = resid<P2>(Rb.x, m2c(M1.y, cc) + Ln, m2c(Mr.x, cc) + M2.x, idx2, idy2);
             if (!EDGE || c.up_a) F.x = cc - coef * r;
             tally(r, rb, sh - 1, c.own_a);
         } else {
-            const double Rn = fr(M1.x);
+            const double Rn = from_right(M1.x);
             const double cc = M1.y;
             const double r = resid<P2>(Rb.y, m2c(Rn, cc) + M1.x, m2c(Mr.y, cc) + M2.y, idx2, idy2);
             if (!EDGE || c.up_b) F.y = cc - coef * r;
@@ -319,7 +282,7 @@ struct March {
     d2 A[T], M1[T], M2[T];
     d2 R[2 * T];     // paired march: R[k] = rhs(r0 - 1 - k)
     d2 Pq[D], Rq[D];  // rows in flight: p(r0 .. r0+D-1), rhs(r0-1 .. r0+D-2)
-    TallyAcc acc[T];
+    double acc[T];
     d2 keep[2];
 };
 
@@ -332,7 +295,7 @@ struct Io {
 
 // one paired-march step: stream in old row r0, push it through the T stages,
 // store the row the last stage finished (r0 - 2T) if this block owns it
-template <int T, int D, int Q, int MODE, bool BP = false, bool P2 = false>
+template <int T, int D, int Q, int MODE, bool P2 = false>
 __device__ __forceinline__ void tb_step(March<T, D>& m, const Lane& c, const Io& io, int r0) {
     const long long pitch = io.pitch;
     const d2 nP = ldv(io.sp + (long long)(r0 + D) * pitch);
@@ -345,7 +308,7 @@ __device__ __forceinline__ void tb_step(March<T, D>& m, const Lane& c, const Io&
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const d2 prevM2 = m.M2[t];
-        v = stage<T, Q, MODE, BP, P2>(c, t, t > 0, v, r0 - 2 * t, m.A[t], m.M1[t], m.M2[t],
+        v = stage<T, Q, MODE, P2>(c, t, t > 0, v, r0 - 2 * t, m.A[t], m.M1[t], m.M2[t],
                                       m.R[2 * t], m.R[2 * t + 1], m.acc[t]);
         if (t == T - 1 && MODE != kPre) {
             const int jw = r0 - 2 * T;  // row finished by the last stage
@@ -393,14 +356,14 @@ __device__ __forceinline__ void tb_step(March<T, D>& m, const Lane& c, const Io&
 }
 
 // paired march over steps r0 = rs .. rend (the colour Q0 of row rs a constant)
-template <int T, int D, int Q0, int MODE, bool BP = false, bool P2 = false>
+template <int T, int D, int Q0, int MODE, bool P2 = false>
 __device__ __forceinline__ void march_pairs(March<T, D>& m, const Lane& c, const Io& io, int r0,
                                             int rend) {
     for (; r0 + 1 <= rend; r0 += 2) {
-        tb_step<T, D, Q0, MODE, BP, P2>(m, c, io, r0);
-        tb_step<T, D, 1 - Q0, MODE, BP, P2>(m, c, io, r0 + 1);
+        tb_step<T, D, Q0, MODE, P2>(m, c, io, r0);
+        tb_step<T, D, 1 - Q0, MODE, P2>(m, c, io, r0 + 1);
     }
-    if (r0 <= rend) tb_step<T, D, Q0, MODE, BP, P2>(m, c, io, r0);
+    if (r0 <= rend) tb_step<T, D, Q0, MODE, P2>(m, c, io, r0);
 }
 
 // Steady march: buffer descriptors over the wave's strip (wave-uniform base,
@@ -422,7 +385,7 @@ __device__ __forceinline__ d2 bload(__amdgpu_buffer_rsrc_t rs, unsigned voff, un
 // one step of the steady march: stream row r0 = rs + n, tally and store.  PH
 // = n mod S (a constant): rhs row rs - 1 + j lives in ring slot j mod S, and
 // stage t reads rows j = n - 2t (red) and n - 2t - 1 (black)
-template <int T, int D, int Q, int PH, bool BP, bool P2, bool EM = false>
+template <int T, int D, int Q, int PH, bool P2, bool EM = false>
 __device__ __forceinline__ void steady_step(March<T, D>& m, d2* R, const Lane& c, const Sio& io,
                                             int r0, unsigned off_n) {
     constexpr int S = ring_slots<T, D>();
@@ -435,7 +398,7 @@ __device__ __forceinline__ void steady_step(March<T, D>& m, d2* R, const Lane& c
     d2 v = m.Pq[0];
 #pragma unroll
     for (int t = 0; t < T; ++t) {
-        v = stage<T, Q, EM ? kSteadyEdge : kSteady, BP, P2>(
+        v = stage<T, Q, EM ? kSteadyEdge : kSteady, P2>(
             c, t, t > 0, v, r0 - 2 * t, m.A[t], m.M1[t], m.M2[t], R[(PH - 2 * t + 4 * S) % S],
             R[(PH - 2 * t - 1 + 4 * S) % S], m.acc[t]);
     }
@@ -472,12 +435,12 @@ __device__ __forceinline__ void steady_step(March<T, D>& m, d2* R, const Lane& c
 }
 
 // S steps of the steady march, the first (step n) at slot phase P0 (colour Q0)
-template <int T, int D, int Q0, int P0, bool BP, bool P2, bool EM = false, int... NN>
+template <int T, int D, int Q0, int P0, bool P2, bool EM = false, int... NN>
 __device__ __forceinline__ void steady_chunk(March<T, D>& m, d2* R, const Lane& c, const Sio& io,
                                              int r0, unsigned off_n,
                                              std::integer_sequence<int, NN...>) {
     constexpr int S = ring_slots<T, D>();
-    (steady_step<T, D, Q0 ^ (NN & 1), (P0 + NN) % S, BP, P2, EM>(
+    (steady_step<T, D, Q0 ^ (NN & 1), (P0 + NN) % S, P2, EM>(
          m, R, c, io, r0 + NN, off_n + (unsigned)NN * io.row_bytes),
      ...);
 }
@@ -522,7 +485,7 @@ __device__ __forceinline__ void put_new(const Lane& c, d2& row, double v) {
     else        row.y = (!EM || c.up_b) ? v : row.y;
 }
 template <int Q, bool EM>
-__device__ __forceinline__ void tally_q(const Lane& c, TallyAcc& acc, double r) {
+__device__ __forceinline__ void tally_q(const Lane& c, double& acc, double r) {
     if (!EM) {
         tally_steady(acc, r);
     } else {
@@ -547,9 +510,9 @@ __device__ __forceinline__ void ghost_cols(const Lane& c, d2& F) {
 // arithmetic as stage().
 template <int QA, int QB, bool P2, bool EM = false>
 __device__ __forceinline__ void stage_pair(const Lane& c, d2& InA, d2& A_a, d2& M1_a, d2& M2_a,
-                                           d2 Ra_a, d2 Rb_a, TallyAcc& acc_a, d2& InB, d2& A_b,
+                                           d2 Ra_a, d2 Rb_a, double& acc_a, d2& InB, d2& A_b,
                                            d2& M1_b, d2& M2_b, d2 Ra_b, d2 Rb_b,
-                                           TallyAcc& acc_b, bool tally_a = true,
+                                           double& acc_b, bool tally_a = true,
                                            bool tally_b = true) {
     auto fl = [](double v) { return from_left(v); };
     auto fr = [](double v) { return from_right(v); };
@@ -578,11 +541,11 @@ __device__ __forceinline__ void stage_pair(const Lane& c, d2& InA, d2& A_a, d2& 
 
 // interior block of H = k * S rows: 4T paired warm-up steps, then k chunks of
 // S statically unrolled steps
-template <int T, int D, int Q0, bool BP, bool P2>
+template <int T, int D, int Q0, bool P2>
 __device__ __forceinline__ void march_interior(March<T, D>& m, const Lane& c, const Io& io,
                                                const Sio& sio, int rs, int nchunks) {
     constexpr int S = ring_slots<T, D>();
-    march_pairs<T, D, Q0, kPre, BP, P2>(m, c, io, rs, rs + 4 * T - 1);  // 4T is even
+    march_pairs<T, D, Q0, kPre, P2>(m, c, io, rs, rs + 4 * T - 1);  // 4T is even
     // ring in static slots: rhs row rs - 1 + j in slot j mod S; at step n = 4T
     // the paired ring holds j = 4T - 1 - k (k < 2T), the rows in flight j = 4T + k
     d2 R[S];
@@ -597,7 +560,7 @@ __device__ __forceinline__ void march_interior(March<T, D>& m, const Lane& c, co
     int r0 = rs + 4 * T;
     unsigned off = 4u * T * sio.row_bytes;
     for (int k = 0; k < nchunks; ++k) {
-        steady_chunk<T, D, Q0, P0, BP, P2>(m, R, c, sio, r0, off,
+        steady_chunk<T, D, Q0, P0, P2>(m, R, c, sio, r0, off,
                                            std::make_integer_sequence<int, S>{});
         r0 += S;
         off += (unsigned)S * sio.row_bytes;
@@ -607,25 +570,19 @@ __device__ __forceinline__ void march_interior(March<T, D>& m, const Lane& c, co
 }  // namespace
 
 // One wave's march over the 128-column strip whose owned columns start at
-// c_out (c_ld = c_out - 2T), rows [j0, j1) of block row `by`; the owned
-// columns end at min(ni, own_hi) (own_hi: the 4-column path runs its strip
-// at a physical side as several of these, clipped to its own columns; ni +
-// anything for the 2-column kernel).  The wave's residual of every stage is
-// added to acc[].
-// STEADY = false: no static-ring path (the caller knows the block's rows are
-// not steady-able; the chained kernel's edge blocks)
-template <int T, int D, bool BP, bool P2 = false, bool STEADY = true>
+// c_out (c_ld = c_out - 2T), rows [j0, j1) of block row `by`.  The wave's
+// residual of every stage is added to acc[].
+template <int T, int D, bool P2 = false>
 __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* __restrict__ src,
                                           double* __restrict__ dst,
                                           const double* __restrict__ rhs, const int c_out,
-                                          const int own_hi, const int j0, const int j1,
-                                          const int by, const int lane, double (&acc)[T]) {
+                                          const int j0, const int j1, const int by,
+                                          const int lane, double (&acc)[T]) {
     constexpr int OW = kStripCells - 4 * T;
     constexpr int S = ring_slots<T, D>();
     const int ni = prm.ni, nj = prm.nj;
     const int c_ld = c_out - 2 * T;
     const long long pitch = prm.pitch;
-    const int own_end = min(ni, own_hi);
 
     Lane c;
     c.ia = c_ld + 2 * lane;
@@ -633,8 +590,8 @@ __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* 
     c.up_a = c.ia >= prm.upd_lo_i && c.ia <= prm.upd_hi_i;
     c.up_b = c.ib >= prm.upd_lo_i && c.ib <= prm.upd_hi_i;
     const bool own_lane = lane >= T && lane < kLanes - T;
-    c.own_a = own_lane && c.ia <= own_end;
-    c.own_b = own_lane && c.ib <= own_end;
+    c.own_a = own_lane && c.ia <= ni;
+    c.own_b = own_lane && c.ib <= ni;
     c.fix0_b = prm.ghost_left && c.ib == 0;
     c.fixr_a = prm.ghost_right && c.ia == ni + 1;
     c.fixr_b = prm.ghost_right && c.ib == ni + 1;
@@ -654,8 +611,6 @@ __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* 
     c.idx2 = prm.idx2;
     c.idy2 = prm.idy2;
     c.coef = prm.coef;
-    c.bl = ((lane + 63) & 63) * 4;
-    c.br = ((lane + 1) & 63) * 4;
 
     March<T, D> m;
 #pragma unroll
@@ -689,10 +644,10 @@ __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* 
     const bool rows_in = rs >= prm.upd_lo_j && rend <= prm.upd_hi_j &&
                          (j1 - j0) % S == 0 && j1 - j0 > 0;
     if (!cols_in) {
-        if (q1) march_pairs<T, D, 1, kEdge, false, P2>(m, c, io, rs, rend);
-        else    march_pairs<T, D, 0, kEdge, false, P2>(m, c, io, rs, rend);
+        if (q1) march_pairs<T, D, 1, kEdge, P2>(m, c, io, rs, rend);
+        else    march_pairs<T, D, 0, kEdge, P2>(m, c, io, rs, rend);
     } else {
-        if (STEADY && rows_in) {
+        if (rows_in) {
             // wave-uniform descriptors over the strip's 128 columns
             auto rsrc = [&](const double* b, int row0, int rows) {
                 const unsigned long long a = (unsigned long long)(
@@ -711,11 +666,11 @@ __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* 
             sio.st_lane = c.own_a ? (unsigned)lane * 16u : 0x40000000u;
             sio.row_bytes = (unsigned)(pitch * 8);
             const int nchunks = (j1 - j0) / S;
-            if (q1) march_interior<T, D, 1, BP, P2>(m, c, io, sio, rs, nchunks);
-            else    march_interior<T, D, 0, BP, P2>(m, c, io, sio, rs, nchunks);
+            if (q1) march_interior<T, D, 1, P2>(m, c, io, sio, rs, nchunks);
+            else    march_interior<T, D, 0, P2>(m, c, io, sio, rs, nchunks);
         } else {
-            if (q1) march_pairs<T, D, 1, kRowEdge, false, P2>(m, c, io, rs, rend);
-            else    march_pairs<T, D, 0, kRowEdge, false, P2>(m, c, io, rs, rend);
+            if (q1) march_pairs<T, D, 1, kRowEdge, P2>(m, c, io, rs, rend);
+            else    march_pairs<T, D, 0, kRowEdge, P2>(m, c, io, rs, rend);
         }
         if (!c.own_a) {
 #pragma unroll
@@ -728,7 +683,7 @@ __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* 
 
 // block rows: nby_big of H = rows_per_block rows, then h_small-row ones
 // (short blocks, which the work order takes last), the last takes the rest
-// (misor_api.hip tb_geometry)
+// (misor_plan.hip tb_geometry)
 __device__ __forceinline__ void block_rows(const SweepParams& prm, int by, int& j0, int& j1) {
     const int H = prm.rows_per_block;
     j0 = by < prm.nby_big ? 1 + by * H : 1 + prm.nby_big * H + (by - prm.nby_big) * prm.h_small;
@@ -773,7 +728,7 @@ __device__ __forceinline__ void block_partials(const SweepParams& prm, const dou
 }
 
 // one block (bx, by) of a pass: logical block L
-template <int T, int WAVES, int D, bool BP, bool P2>
+template <int T, int WAVES, int D, bool P2>
 __device__ __forceinline__ void tb_block(const SweepParams& prm, const double* __restrict__ src,
                                          double* __restrict__ dst, const double* __restrict__ rhs,
                                          double* __restrict__ partials, const int L,
@@ -797,7 +752,7 @@ __device__ __forceinline__ void tb_block(const SweepParams& prm, const double* _
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[t] = 0.0;
     if (c_out <= prm.ni)  // wave-uniform
-        tb_strip2<T, D, BP, P2>(prm, src, dst, rhs, c_out, 0x7fffffff, j0, j1, by, lane, acc);
+        tb_strip2<T, D, P2>(prm, src, dst, rhs, c_out, j0, j1, by, lane, acc);
     block_partials<T, WAVES>(prm, acc, partials, L, wsum);
 }
 
@@ -878,7 +833,7 @@ __device__ __forceinline__ void for_each_block(const SweepParams& prm, int* __re
 // Work: segments = ranges of block rows of one column, one 64-bit word each
 // (chain_word): the next unclaimed block row N, the end E (exclusive), the
 // column.  A launch starts from a host-built list of segments (about one per
-// resident workgroup, misor_api.hip chain_plan), in one run per XCD (the
+// resident workgroup, misor_plan.hip chain_plan), in one run per XCD (the
 // slow blocks first; neighbouring columns on one XCD share its L2: the
 // strips' overlapping columns).  A workgroup takes a segment by ticket and
 // claims its blocks one by one
@@ -903,7 +858,7 @@ __device__ __forceinline__ void for_each_block(const SweepParams& prm, int* __re
 // ---------------------------------------------------------------------------
 // a block row [j0, j1) that can be part of a run: its cone clear of the
 // physical bottom / top sides and a height the static ring divides
-// (tb_strip2's rows_in); misor_api.hip chain_plan uses the same test
+// (tb_strip2's rows_in); misor_plan.hip chain_plan uses the same test
 template <int T, int D>
 __host__ __device__ inline bool chain_rows_ok(const SweepParams& prm, int j0, int j1) {
     constexpr int S = ring_slots<T, D>();
@@ -1093,10 +1048,10 @@ template <int T, int WAVES, int D, int Q0, bool P2, bool EM>
 __device__ __forceinline__ void chain_strip(const SweepParams& prm, const double* __restrict__ src,
                                             double* __restrict__ dst,
                                             const double* __restrict__ rhs,
-                                            double* __restrict__ partials, double (*wsum)[WAVES],
-                                            int* sh, unsigned long long* seg, Lane& c,
-                                            const Io& io, bool general, int c_ld, int bx, int by,
-                                            int slot, int own_end, int lane) {
+                                            double* __restrict__ partials, int* sh,
+                                            unsigned long long* seg, Lane& c, const Io& io,
+                                            bool general, int c_ld, int bx, int by, int slot,
+                                            int own_end, int lane) {
     constexpr int S = ring_slots<T, D>();
     const long long pitch = prm.pitch;
     int j0, j1;
@@ -1124,7 +1079,7 @@ __device__ __forceinline__ void chain_strip(const SweepParams& prm, const double
     for (int k = 0; k < 2 * T; ++k) m.R[k] = d2{0.0, 0.0};
 
     if (!EM && general) {  // rows not steady-able: the general march, block by block
-        march_pairs<T, D, Q0, kEdge, false, P2>(m, c, io, rs, j1 - 1 + 2 * T);
+        march_pairs<T, D, Q0, kEdge, P2>(m, c, io, rs, j1 - 1 + 2 * T);
         for (;;) {
             const int nb = chain_block_end<T, WAVES>(prm, m.acc, partials, by * prm.nbx + bx, sh,
                                                      seg, slot, by, own_end);
@@ -1132,7 +1087,7 @@ __device__ __forceinline__ void chain_strip(const SweepParams& prm, const double
             by = nb;
             block_rows(prm, by, j0, j1);
             set_block(by, j0, j1);
-            march_pairs<T, D, Q0, kEdge, false, P2>(m, c, io, j0 + 2 * T, j1 - 1 + 2 * T);
+            march_pairs<T, D, Q0, kEdge, P2>(m, c, io, j0 + 2 * T, j1 - 1 + 2 * T);
         }
     }
     auto rsrc = [&](const double* b, int row0, int rows) {
@@ -1149,7 +1104,7 @@ __device__ __forceinline__ void chain_strip(const SweepParams& prm, const double
     // garbage columns never reach an owned one; a strip at a physical side
     // needs the masks and ghost-column copies of kEdge -- its rows are
     // interior, so nothing is tallied or stored)
-    march_pairs<T, D, Q0, EM ? kEdge : kPre, false, P2>(m, c, io, rs, rs + 4 * T - 1);
+    march_pairs<T, D, Q0, EM ? kEdge : kPre, P2>(m, c, io, rs, rs + 4 * T - 1);
     d2 R[S];
 #pragma unroll
     for (int k = 0; k < S; ++k) R[k] = d2{0.0, 0.0};
@@ -1176,7 +1131,7 @@ __device__ __forceinline__ void chain_strip(const SweepParams& prm, const double
             int r0 = vrs + 4 * T;
             unsigned off = 4u * T * sio.row_bytes;
             for (int k = 0; k < (j1 - j0) / S; ++k) {
-                steady_chunk<T, D, Q0, P0, false, P2, EM>(m, R, c, sio, r0, off,
+                steady_chunk<T, D, Q0, P0, P2, EM>(m, R, c, sio, r0, off,
                                                          std::make_integer_sequence<int, S>{});
                 r0 += S;
                 off += (unsigned)S * sio.row_bytes;
@@ -1223,8 +1178,6 @@ __device__ __forceinline__ void chain_lane(const SweepParams& prm, const double*
     c.idx2 = prm.idx2;
     c.idy2 = prm.idy2;
     c.coef = prm.coef;
-    c.bl = ((lane + 63) & 63) * 4;
-    c.br = ((lane + 1) & 63) * 4;
     const long long base = (long long)kYOff * pitch + kXOff + c.ia;
     io = Io{src + base, rhs + base, dst + base, pitch};
 }
@@ -1239,9 +1192,9 @@ __device__ __forceinline__ void chain_lane(const SweepParams& prm, const double*
 template <int T, int WAVES, int D, bool P2, int EDGE>
 __device__ __forceinline__ void chain_run(const SweepParams& prm, const double* __restrict__ src,
                                           double* __restrict__ dst, const double* __restrict__ rhs,
-                                          double* __restrict__ partials, double (*wsum)[WAVES],
-                                          int* sh, unsigned long long* seg, int bx, int by,
-                                          int slot, int own_end) {
+                                          double* __restrict__ partials, int* sh,
+                                          unsigned long long* seg, int bx, int by, int slot,
+                                          int own_end) {
     constexpr int OW = kStripCells - 4 * T;
     const int lane = threadIdx.x & 63;
     // wave-uniform (as known to the compiler: the strip's descriptors and
@@ -1266,14 +1219,6 @@ __device__ __forceinline__ void chain_run(const SweepParams& prm, const double* 
     chain_lane<T>(prm, src, dst, rhs, c_ld, lane, c, io);
     int j0, j1;
     block_rows(prm, by, j0, j1);
-    // steady chunks for strips clear of the physical left / right sides, in
-    // runs of steady-able block rows; the general lane-masked, row-tested
-    // march (kEdge) for the rest: strips at a physical side, and the few
-    // block rows whose cone reaches a physical bottom / top side (or a
-    // column's last block of a height the ring does not divide) -- the host
-    // keeps those in segments of their own.  (A row-tested-only march for
-    // the latter, kRowEdge, in the same kernel as the steady runs makes the
-    // register allocator spill the runs' ring.)
     // steady chunks in runs of steady-able block rows; the general
     // lane-masked, row-tested march (kEdge) for the few block rows whose cone
     // reaches a physical bottom / top side (or a column's last block of a
@@ -1290,29 +1235,28 @@ __device__ __forceinline__ void chain_run(const SweepParams& prm, const double* 
     static_assert(ring_slots<T, 1>() == ring_slots<T, D>(), "edge ring");
     if constexpr (EDGE != 0) {  // kSteadyEdge for every strip
         if (q1)
-            chain_strip<T, WAVES, 1, 1, P2, true>(prm, src, dst, rhs, partials, wsum, sh, seg, c,
+            chain_strip<T, WAVES, 1, 1, P2, true>(prm, src, dst, rhs, partials, sh, seg, c,
                                                   io, false, c_ld, bx, by, slot, own_end, lane);
         else
-            chain_strip<T, WAVES, 1, 0, P2, true>(prm, src, dst, rhs, partials, wsum, sh, seg, c,
+            chain_strip<T, WAVES, 1, 0, P2, true>(prm, src, dst, rhs, partials, sh, seg, c,
                                                   io, false, c_ld, bx, by, slot, own_end, lane);
     } else {  // (the host puts every column with a strip at a physical side in the EDGE list)
         if (q1)
-            chain_strip<T, WAVES, D, 1, P2, false>(prm, src, dst, rhs, partials, wsum, sh, seg, c,
+            chain_strip<T, WAVES, D, 1, P2, false>(prm, src, dst, rhs, partials, sh, seg, c,
                                                    io, general, c_ld, bx, by, slot, own_end, lane);
         else
-            chain_strip<T, WAVES, D, 0, P2, false>(prm, src, dst, rhs, partials, wsum, sh, seg, c,
+            chain_strip<T, WAVES, D, 0, P2, false>(prm, src, dst, rhs, partials, sh, seg, c,
                                                    io, general, c_ld, bx, by, slot, own_end, lane);
     }
 }
 
 // chained persistent pass (2-column strips); work = the launch's work area
-// (int head[kChainHead], then the segment words; misor_api.hip chain plans)
+// (int head[kChainHead], then the segment words; misor_plan.hip chain_plan)
 template <int T, int WAVES, int D, bool P2, int EDGE = 0>
 __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tbc_kernel(
     SweepParams prm, const double* __restrict__ src, double* __restrict__ dst,
     const double* __restrict__ rhs, double* __restrict__ partials,
     const DevState* __restrict__ st, int force, int* __restrict__ work) {
-    __shared__ double wsum[T][WAVES];  // (unused by the chained march: per-wave partials)
     // sh[0..3]: the run (chain_acquire), sh[4..5]: trace clock, sh[6]: run start,
     // sh[7]: own_end of the last claim, sh[8]: unclaimed blocks seen then
     __shared__ __attribute__((aligned(8))) int sh[12];
@@ -1334,12 +1278,12 @@ __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tbc_kernel(
         const int own_end = __builtin_amdgcn_readfirstlane(sh[3]);
         __syncthreads();  // sh is rewritten by the run's block ends
         if (bx < 0) break;
-        chain_run<T, WAVES, D, P2, EDGE>(prm, src, dst, rhs, partials, wsum, sh, seg, bx, by, slot,
+        chain_run<T, WAVES, D, P2, EDGE>(prm, src, dst, rhs, partials, sh, seg, bx, by, slot,
                                          own_end);
     }
 }
 
-template <int T, int WAVES, int D, bool BP, bool P2 = false>
+template <int T, int WAVES, int D, bool P2 = false>
 __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tb_kernel(
     SweepParams prm, const double* __restrict__ src, double* __restrict__ dst,
     const double* __restrict__ rhs, double* __restrict__ partials,
@@ -1348,7 +1292,7 @@ __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tb_kernel(
     __shared__ int ticket;
     if (force || !st->done) {
         for_each_block(prm, queue, &ticket, [&](int L) {
-            tb_block<T, WAVES, D, BP, P2>(prm, src, dst, rhs, partials, L, wsum);
+            tb_block<T, WAVES, D, P2>(prm, src, dst, rhs, partials, L, wsum);
         });
     }
     // Persistent launch: the queue resets itself for the next one (instead of

@@ -8,16 +8,24 @@
 
 namespace misor {
 
-int tb_max_t(int variant) { return kTbVariants[variant].max_t; }
+// the built variant of that public number; a retired one: max_t = 0
+static const TbVariant& tb_variant(int variant) {
+    static constexpr TbVariant retired = {-1, 4, 2, 0, 0, 0};
+    for (const TbVariant& v : kTbVariants)
+        if (v.id == variant) return v;
+    return retired;
+}
+
+int tb_max_t(int variant) { return tb_variant(variant).max_t; }
 
 int tb_out_width(int T, int /*variant*/) { return kStripCells - 4 * T; }
 
-int tb_waves(int variant) { return kTbVariants[variant].waves; }
+int tb_waves(int variant) { return tb_variant(variant).waves; }
 
 int tb_ring_slots(int T, int variant) {
-    const int D = kTbVariants[variant].ahead;
-    if (kTbVariants[variant].hr) return hr_slots(T, D, kTbVariants[variant].skew && T >= 2 ? 1 : 0);
-    return 2 * T + D + (D & 1);  // sor_tb.h ring_slots
+    const TbVariant& v = tb_variant(variant);
+    if (v.hr) return hr_slots(T, v.ahead, v.skew && T >= 2 ? 1 : 0);
+    return 2 * T + v.ahead + (v.ahead & 1);  // sor_tb.h ring_slots
 }
 
 int tb_nbx(int ni, int T, int variant) {

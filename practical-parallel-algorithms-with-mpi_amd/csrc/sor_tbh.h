@@ -58,7 +58,7 @@ template <int T, int D>
 struct HrMarch {
     d2 A[T], M1[T], M2[T];
     d2 Pq[D];
-    TallyAcc acc[T];
+    double acc[T];
     d2 keep[2];
     d2 B;  // skewed form: stage SKH-1's output of the previous step
 };
@@ -73,8 +73,6 @@ struct HrIo {
     double* dp;                      // kEdge / kRowEdge stores: dst at row 0 of the lane's columns
     long long pitch;
 };
-
-__device__ __forceinline__ void hr_stv(double* p, d2 v) { stv(p, v); }
 
 // step n of the split-ring march (stream row r0 = rs0 + n; PH = n mod S)
 template <int T, int D, int MODE, int Q, int PH, bool P2>
@@ -104,7 +102,7 @@ __device__ __forceinline__ void hr_step(HrMarch<T, D>& m, d2* R, const Lane& c, 
             Rb = Q == 0 ? d2{lb[t], 0.0} : d2{0.0, lb[t]};
         }
         if (t == T - 1) prevM2 = m.M2[t];
-        v = stage<T, Q, MODE, false, P2>(c, t, t > 0, v, r0 - 2 * t, m.A[t], m.M1[t], m.M2[t], Ra,
+        v = stage<T, Q, MODE, P2>(c, t, t > 0, v, r0 - 2 * t, m.A[t], m.M1[t], m.M2[t], Ra,
                                          Rb, m.acc[t]);
     }
     // row n - 2K + 1 leaves the register ring for the LDS one (read next step
@@ -130,14 +128,14 @@ __device__ __forceinline__ void hr_step(HrMarch<T, D>& m, d2* R, const Lane& c, 
             double* drow = io.dp + (long long)jw * io.pitch;
             if (MODE == kRowEdge) {
                 if (c.st_a) {
-                    hr_stv(drow, v);
-                    if (c.gb && jw == 1) hr_stv(drow - io.pitch, v);
-                    if (c.gt && jw == c.nj) hr_stv(drow + io.pitch, v);
+                    stv(drow, v);
+                    if (c.gb && jw == 1) stv(drow - io.pitch, v);
+                    if (c.gt && jw == c.nj) stv(drow + io.pitch, v);
                 }
             } else {
                 auto put = [&](double* p, d2 o) {
                     if (c.st_a && c.st_b) {
-                        hr_stv(p, o);
+                        stv(p, o);
                     } else if (c.st_a) {
                         p[0] = o.x;
                     } else if (c.st_b) {
@@ -231,7 +229,7 @@ __device__ __forceinline__ void hrs_step(HrMarch<T, D>& m, d2* R, const Lane& c,
                                          kAll || ta == T - 1, kAll || tb == T - 1);
         }
         if (T - SKH > SKH)
-            u = stage<T, Q, MODE, false, P2, SKH>(c, T - 1, true, u, r0 - 2 * (T - 1),
+            u = stage<T, Q, MODE, P2, SKH>(c, T - 1, true, u, r0 - 2 * (T - 1),
                                                   m.A[T - 1], m.M1[T - 1], m.M2[T - 1],
                                                   rr(T - 1, true), rr(T - 1, false),
                                                   m.acc[T - 1]);
@@ -242,13 +240,13 @@ __device__ __forceinline__ void hrs_step(HrMarch<T, D>& m, d2* R, const Lane& c,
         for (int t = SKH; t < T; ++t) {
             if (!runs(t)) continue;
             if (t == T - 1) prevM2 = m.M2[t];
-            u = stage<T, Q, MODE, false, P2, SKH>(c, t, true, u, r0 - 2 * t, m.A[t], m.M1[t],
+            u = stage<T, Q, MODE, P2, SKH>(c, t, true, u, r0 - 2 * t, m.A[t], m.M1[t],
                                                   m.M2[t], rr(t, true), rr(t, false), m.acc[t]);
         }
 #pragma unroll
         for (int t = 0; t < SKH; ++t) {
             if (!runs(t)) continue;
-            v = stage<T, 1 - Q, MODE, false, P2, SKH>(c, t, t > 0, v, r0 + 1 - 2 * t, m.A[t],
+            v = stage<T, 1 - Q, MODE, P2, SKH>(c, t, t > 0, v, r0 + 1 - 2 * t, m.A[t],
                                                       m.M1[t], m.M2[t], rr(t, true),
                                                       rr(t, false), m.acc[t]);
         }
@@ -275,14 +273,14 @@ __device__ __forceinline__ void hrs_step(HrMarch<T, D>& m, d2* R, const Lane& c,
             double* drow = io.dp + (long long)jw * io.pitch;
             if (MODE == kRowEdge) {
                 if (c.st_a) {
-                    hr_stv(drow, u);
-                    if (c.gb && jw == 1) hr_stv(drow - io.pitch, u);
-                    if (c.gt && jw == c.nj) hr_stv(drow + io.pitch, u);
+                    stv(drow, u);
+                    if (c.gb && jw == 1) stv(drow - io.pitch, u);
+                    if (c.gt && jw == c.nj) stv(drow + io.pitch, u);
                 }
             } else {
                 auto put = [&](double* p, d2 o) {
                     if (c.st_a && c.st_b) {
-                        hr_stv(p, o);
+                        stv(p, o);
                     } else if (c.st_a) {
                         p[0] = o.x;
                     } else if (c.st_b) {
@@ -377,20 +375,21 @@ __device__ __forceinline__ void hr_warm(HrMarch<T, D>& m, d2* R, const Lane& c, 
 }
 
 // the per-lane constants of the strip whose owned columns start at c_out,
-// for block rows [j0, j1) of block row `by` (tb_strip2's lane setup)
+// for block rows [j0, j1) of block row `by` (tb_strip2's lane setup; a copy,
+// as hr_cols_in, hr_rsrc and the steps' stores are: shared helpers changed the
+// spills of launched kernels, profiles/r07_refactor_resources.txt)
 template <int T>
 __device__ __forceinline__ void hr_lane(const SweepParams& prm, const int c_out, const int j0,
                                         const int j1, const int by, const int lane, Lane& c) {
     const int ni = prm.ni, nj = prm.nj;
     const int c_ld = c_out - 2 * T;
-    const int own_end = ni;
     c.ia = c_ld + 2 * lane;
     c.ib = c.ia + 1;
     c.up_a = c.ia >= prm.upd_lo_i && c.ia <= prm.upd_hi_i;
     c.up_b = c.ib >= prm.upd_lo_i && c.ib <= prm.upd_hi_i;
     const bool own_lane = lane >= T && lane < kLanes - T;
-    c.own_a = own_lane && c.ia <= own_end;
-    c.own_b = own_lane && c.ib <= own_end;
+    c.own_a = own_lane && c.ia <= ni;
+    c.own_b = own_lane && c.ib <= ni;
     c.fix0_b = prm.ghost_left && c.ib == 0;
     c.fixr_a = prm.ghost_right && c.ia == ni + 1;
     c.fixr_b = prm.ghost_right && c.ib == ni + 1;
@@ -409,8 +408,6 @@ __device__ __forceinline__ void hr_lane(const SweepParams& prm, const int c_out,
     c.idx2 = prm.idx2;
     c.idy2 = prm.idy2;
     c.coef = prm.coef;
-    c.bl = ((lane + 63) & 63) * 4;
-    c.br = ((lane + 1) & 63) * 4;
 }
 
 // columns interior: every column of the cone an updated cell and ownership
@@ -636,9 +633,9 @@ __device__ __forceinline__ void hr_chain_steady(const SweepParams& prm,
 
 // one run of a chained split-ring pass: column bx from block row by (all
 // waves; sor_tb.h chain_run): runs of steady blocks chained (hr_chain_steady),
-// every other block alone (hr_strip); EDGE = 1 (an A/B form): every block
-// alone.  Every wave calls chain_block_end at every block end of the run.
-template <int T, int WAVES, int D, bool P2, int SK, int EDGE, bool LITE = false>
+// every other block alone (hr_strip).  Every wave calls chain_block_end at
+// every block end of the run.
+template <int T, int WAVES, int D, bool P2, int SK, bool LITE = false>
 __device__ __forceinline__ void hr_chain_run(const SweepParams& prm,
                                              const double* __restrict__ src,
                                              double* __restrict__ dst,
@@ -653,8 +650,7 @@ __device__ __forceinline__ void hr_chain_run(const SweepParams& prm,
     if (bx == 0 && by == 0) copy_corners(prm, src, dst);
     int j0, j1;
     block_rows(prm, by, j0, j1);
-    const bool chained =
-        EDGE == 0 && c_out <= prm.ni && hr_chain_rows_ok<T, D, SK>(prm, j0, j1);
+    const bool chained = c_out <= prm.ni && hr_chain_rows_ok<T, D, SK>(prm, j0, j1);
     if (chained) {
         // the colour of the run's first streamed row (rs0 = j0 - 2T - SK)
         const bool q1 = ((prm.parity + j0 - 2 * T - SK) & 1) != 0;
@@ -696,9 +692,9 @@ __device__ __forceinline__ void hr_chain_run(const SweepParams& prm,
 }  // namespace
 
 // the chained split-ring pass (sor_tb.h rb_tbc_kernel's work area and
-// segment lists; EDGE: the kernel of the columns at a physical left / right
-// side, launched beside the main one)
-template <int T, int WAVES, int D, bool P2, int SK, int EDGE, bool LITE = false>
+// segment lists; one kernel for both lists of a pass: the main one and that of
+// the columns at a physical left / right side, launched side by side)
+template <int T, int WAVES, int D, bool P2, int SK, bool LITE = false>
 __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tbhc_kernel(
     SweepParams prm, const double* __restrict__ src, double* __restrict__ dst,
     const double* __restrict__ rhs, double* __restrict__ partials,
@@ -737,8 +733,8 @@ __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tbhc_kernel(
             seg = reinterpret_cast<unsigned long long*>(prm.alt_work + kChainHead);
             continue;
         }
-        hr_chain_run<T, WAVES, D, P2, SK, EDGE, LITE>(prm, src, dst, rhs, partials, sh, seg, bx,
-                                                      by, slot, own_end, lx);
+        hr_chain_run<T, WAVES, D, P2, SK, LITE>(prm, src, dst, rhs, partials, sh, seg, bx, by,
+                                                slot, own_end, lx);
     }
 }
 

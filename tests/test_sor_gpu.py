@@ -250,3 +250,31 @@ def test_pow2_spacing_vs_oracle(ni, nj, T, variant):
         got = g.download(M.P)
     assert it == k
     assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+
+
+def test_pow2_spacing_unchained_vs_oracle():
+    """the power-of-two form of the default kernel's unchained pass (sor_tb.h
+    rb_tb_kernel, 4 strips): grids of the suite's sizes run variant 0 in
+    chained passes (rb_tbc_kernel), so chaining is switched off here.  Block
+    rows of 3 ring lengths (T = 2: 6 slots): interior blocks, a ragged last
+    block row of 12 rows and both physical side columns."""
+    ni, nj, T = 2050, 300, 2
+    rng = np.random.default_rng(ni + 7 * nj + T)
+    p = rng.standard_normal((nj + 2, ni + 2)) * np.exp(rng.uniform(-20, 20, (nj + 2, ni + 2)))
+    rhs = rng.standard_normal((nj + 2, ni + 2)) * 1e6
+    h = 2.0 ** -10
+    k = 2 * T + 1
+    want = p.copy()
+    orc.solve_rb(want, rhs, h, h, 1.7, 1e-300, k)
+    with M.Grid(ni, nj, h, h, 1.7, 1e-300, k) as g:
+        g.set_tuning(M.TUNE_TB_CHAIN, 0)
+        set_mode(g, "t%d" % T)
+        g.set_tuning(M.TUNE_TB_ROWS, 3 * (2 * T + 2))
+        g.upload(M.P, p)
+        g.upload(M.RHS, rhs)
+        it, _ = g.solve_rb()
+        got = g.download(M.P)
+        st = g.stats()
+    assert (st["tb_variant"], st["chained"], st["iters_per_pass"]) == (0, 0, T), st
+    assert it == k
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
