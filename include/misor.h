@@ -200,7 +200,14 @@ int misor_solve_rb_n(misor_grid* g, int itermax, int* iters, double* res);
  * call): assignment-4/src/solver.c:126-177 (xorder = MISOR_LEX_A4) and
  * assignment-5/sequential/src/solver.c:140-191 (xorder = MISOR_LEX_SEQ; the
  * two differ only in the order of the stencil terms), bit for bit, as an
- * anti-diagonal wavefront in one workgroup.  Single rank, variant RB only. */
+ * anti-diagonal wavefront: in one workgroup on grids below 512^2 cells (all
+ * the reference's .par grids), as a wavefront of tiles over the whole device
+ * from there on (MISOR_TUNE_LEX_TILED and the keys after it).  p and the
+ * iteration count never depend on the form; res may differ in its last bits
+ * between the two forms and between tile sizes, because r^2 is summed in
+ * another order (for one form and tile size it is the same bits on every
+ * run).  Single rank, variant RB only.  MISOR_EHIP "wavefront stalled": a
+ * bounded wait inside the tiled launch gave up; p is then undefined. */
 enum { MISOR_LEX_A4 = 0, MISOR_LEX_SEQ = 1 };
 int misor_solve_lex(misor_grid* g, int xorder, int* iters, double* res);
 
@@ -281,7 +288,31 @@ enum {
                                     * splits every main segment down to fewer than 4
                                     * unclaimed blocks before the main kernel starts (the
                                     * steals forced, for tests).  p and res are the same
-                                    * bits for every value */
+                                    * bits for every value */,
+    MISOR_TUNE_LEX_TILED = 17,     /* misor_solve_lex: -1 (default) = the automatic rule
+                                    * (the tiled wavefront from 512^2 interior cells on,
+                                    * where it measured faster; the one-workgroup kernel
+                                    * below, and always when p fits in its LDS);
+                                    * 0 = always the one-workgroup kernel; 1 = always
+                                    * tiled, also on grids that fit in LDS and on a grid of
+                                    * one tile.  Get: 1 if the next misor_solve_lex of this
+                                    * grid would run tiled.  p and the iteration count are
+                                    * the same bits for every value */
+    MISOR_TUNE_LEX_TILE_W = 18,    /* tiled lexicographic solve: tile width in cells ... */
+    MISOR_TUNE_LEX_TILE_H = 19,    /* ... and height (defaults 96 x 96).  Sides from 8 up
+                                    * to what LDS holds (tile + one-cell halo + the tile's
+                                    * rhs within 160 KB: 96 x 96, 128 x 64 fit); <= 0 returns
+                                    * to the default; a pair that does not fit is
+                                    * MISOR_EINVAL and changes nothing.  p and the
+                                    * iteration count are the same bits for every value */
+    MISOR_TUNE_LEX_WGS = 20        /* tiled lexicographic solve: workgroups of its
+                                    * persistent grid (at most one per tile); <= 0
+                                    * (default) = automatic: at most the tiles of the
+                                    * longest tile anti-diagonal and at most what the device
+                                    * holds resident.  Progress needs no residency: 1
+                                    * runs the tiles one after the other.  p and the
+                                    * iteration count are the same bits for every value
+                                    * (res too) */
 };
 int misor_set_tuning(misor_grid* g, int key, int value);
 int misor_get_tuning(const misor_grid* g, int key, int* value);

@@ -6,53 +6,26 @@
 // p.dat / pressure.dat / velocity.dat come from it).  Cell (i,j) uses the NEW
 // values of (i-1,j) and (i,j-1) and the OLD values of (i+1,j) and (i,j+1), so
 // every cell of one anti-diagonal i+j = d can be updated at once once diagonal
-// d-1 is done: one workgroup sweeps the diagonals 2 .. ni+nj with a barrier
-// between them, with the reference's exact expression order per cell (two
-// x/y orders: `xorder` 0 = assignment-4, 1 = assignment-5 sequential).  After
-// the sweep: the Neumann ghost copy (rows, then columns), res = sum r^2 /
-// (imax*jmax), the same loop test.  p lives in LDS when it fits (the NS and
-// Poisson .par grids), in HBM otherwise.  Inherently sequential: this mode is
-// for reproducing the reference's lexicographic results exactly, not for
-// speed (the red-black kernels are the production path).
+// d-1 is done.  This file is the small-grid form: one workgroup sweeps the
+// diagonals 2 .. ni+nj with a barrier between them, with the reference's exact
+// expression order per cell (lex_cell.h; two x/y orders: `xorder` 0 =
+// assignment-4, 1 = assignment-5 sequential).  After the sweep: the Neumann
+// ghost copy (rows, then columns), res = sum r^2 / (imax*jmax), the same loop
+// test.  p lives in LDS when it fits (the NS and Poisson .par grids), in HBM
+// otherwise.  Grids whose p does not fit in LDS run by default as a tiled
+// wavefront over the whole device instead (lex_tiled.hip; misor_solve_lex
+// chooses, MISOR_TUNE_LEX_TILED); the mode reproduces the reference's
+// lexicographic results exactly (the red-black kernels are the production
+// path).
 
-#include "misor_internal.h"
+#include "lex_cell.h"
 
 namespace misor {
-
-namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-}  // namespace
 
 // threads of the one workgroup: the longest anti-diagonal rounded up to whole
 // waves (at most 1024): a barrier per diagonal costs less across fewer waves
 // (the reference's 100 x 100 NS grid: 2 waves instead of 16)
 constexpr int kLexThreads = 1024;
-
-// W: row stride of P (LDS: ni+2; HBM: pitch); P points at cell (0,0)
-template <bool XORDER>
-__device__ __forceinline__ double lex_cell(double* P, const double* rhs_glob, long long rpitch,
-                                           long long W, int i, int j, double idx2, double idy2,
-                                           double factor) {
-    const long long k = (long long)j * W + i;
-    const double c = P[k];
-    double xt, yt;
-    if (XORDER) {  // assignment-5/sequential/src/solver.c:162-164
-        xt = (P[k + 1] - 2.0 * c) + P[k - 1];
-        yt = (P[k + W] - 2.0 * c) + P[k - W];
-    } else {  // assignment-4/src/solver.c:149-151
-        xt = (P[k - 1] - 2.0 * c) + P[k + 1];
-        yt = (P[k - W] - 2.0 * c) + P[k + W];
-    }
-    const double r = rhs_glob[(long long)j * rpitch + i] - (xt * idx2 + yt * idy2);
-    P[k] = c - (factor * r);
-    return r;
-}
 
 template <bool XORDER>
 __global__ __launch_bounds__(kLexThreads) void lex_solve_kernel(
@@ -117,7 +90,7 @@ __global__ __launch_bounds__(kLexThreads) void lex_solve_kernel(
             P[(long long)j * W + ni + 1] = P[(long long)j * W + ni];
         }
         // fixed-order block sum of r^2
-        acc = wave_sum(acc);
+        acc = lex_wave_sum(acc);
         if (lane == 0) red[wave] = acc;
         __syncthreads();
         if (t == 0) {
@@ -144,13 +117,19 @@ __global__ __launch_bounds__(kLexThreads) void lex_solve_kernel(
     }
 }
 
+int lex_use_lds(int ni, int nj) {
+    const size_t need = sizeof(double) * (32 + (size_t)(ni + 2) * (nj + 2));
+    const size_t need_r = need + sizeof(double) * (size_t)ni * nj;  // + rhs
+    // 2: p and rhs in LDS, 1: p in LDS, 0: both in HBM
+    return need_r <= 160 * 1024 ? 2 : need <= 160 * 1024 ? 1 : 0;
+}
+
 void launch_solve_lex(hipStream_t s, double* p, const double* rhs, int ni, int nj,
                       long long pitch, double idx2, double idy2, double factor, double cells,
                       int xorder, DevState* st) {
     const size_t need = sizeof(double) * (32 + (size_t)(ni + 2) * (nj + 2));
     const size_t need_r = need + sizeof(double) * (size_t)ni * nj;  // + rhs
-    // 2: p and rhs in LDS, 1: p in LDS, 0: both in HBM
-    const int use_lds = need_r <= 160 * 1024 ? 2 : need <= 160 * 1024 ? 1 : 0;
+    const int use_lds = lex_use_lds(ni, nj);
 
     const int diag = ni < nj ? ni : nj;
     const int nt = std::min(kLexThreads, std::max(64, (diag + 63) / 64 * 64));

@@ -99,6 +99,7 @@ void misor_destroy(misor_grid* g) {
         if (f) (void)hipFree(f);
     (void)hipFree(g->partials);
     (void)hipFree(g->tb_queue);
+    (void)hipFree(g->lex_work.buf);
     for (auto& v : g->chain_plan)
         for (auto& row : v)
             for (auto& pl : row) {
@@ -768,6 +769,26 @@ int misor_set_tuning(misor_grid* g, int key, int value) {
         if (value < 0 || value > 2) return fail(MISOR_EINVAL, "EDGE_STEAL is 0, 1 or 2");
         g->edge_steal = value;
         return MISOR_OK;
+    case MISOR_TUNE_LEX_TILED:
+        if (value < -1 || value > 1) return fail(MISOR_EINVAL, "LEX_TILED is -1, 0 or 1");
+        g->lex_tiled = value;
+        return MISOR_OK;
+    case MISOR_TUNE_LEX_TILE_W:
+    case MISOR_TUNE_LEX_TILE_H: {
+        // the pair must fit (with the other at its current value); a rejected
+        // request changes nothing
+        const int v = value > 0 ? value : 0;
+        const int tw = key == MISOR_TUNE_LEX_TILE_W ? v : g->lex_tw;
+        const int th = key == MISOR_TUNE_LEX_TILE_H ? v : g->lex_th;
+        if (!lex_tile_fits(tw ? tw : kLexTileW, th ? th : kLexTileH))
+            return fail(MISOR_EINVAL,
+                        "lexicographic tile %d x %d: sides from %d, tile + halo + rhs within LDS",
+                        tw ? tw : kLexTileW, th ? th : kLexTileH, kLexMinTile);
+        g->lex_tw = tw;
+        g->lex_th = th;
+        return MISOR_OK;
+    }
+    case MISOR_TUNE_LEX_WGS: g->lex_wgs = value > 0 ? value : 0; return MISOR_OK;
     default: return fail(MISOR_EINVAL, "unknown tuning key %d", key);
     }
 }
@@ -788,6 +809,10 @@ int misor_get_tuning(const misor_grid* g, int key, int* value) {
     case MISOR_TUNE_NEAR_BAND: *value = g->near_exp; return MISOR_OK;
     case MISOR_TUNE_RES_LITE: *value = g->res_lite; return MISOR_OK;
     case MISOR_TUNE_EDGE_STEAL: *value = g->edge_steal; return MISOR_OK;
+    case MISOR_TUNE_LEX_TILED: *value = lex_tiled_on(g); return MISOR_OK;
+    case MISOR_TUNE_LEX_TILE_W: *value = g->lex_tw ? g->lex_tw : kLexTileW; return MISOR_OK;
+    case MISOR_TUNE_LEX_TILE_H: *value = g->lex_th ? g->lex_th : kLexTileH; return MISOR_OK;
+    case MISOR_TUNE_LEX_WGS: *value = g->lex_wgs; return MISOR_OK;
     case MISOR_TUNE_NS_FUSE: *value = g->ns_fuse; return MISOR_OK;
     case MISOR_TUNE_FINISH2: *value = g->finish2; return MISOR_OK;
     case MISOR_TUNE_TB_RESERVE: *value = g->tb_reserve; return MISOR_OK;

@@ -165,6 +165,12 @@ struct misor_grid {
     // workgroups steal from the main list, 0 never, 2 (diagnostics) the main
     // kernel launched behind the edge kernel (misor_solve.hip)
     int edge_steal = 1;
+    // lexicographic solve (misor_solve_lex): MISOR_TUNE_LEX_TILED (-1 the
+    // automatic rule, 0 the one-workgroup kernel, 1 the tiled wavefront),
+    // MISOR_TUNE_LEX_TILE_W / _H (0: the default tile), MISOR_TUNE_LEX_WGS
+    // (0: automatic grid), and the tiled kernel's work area
+    int lex_tiled = -1, lex_tw = 0, lex_th = 0, lex_wgs = 0;
+    LexTiledWork lex_work{};
     // MISOR_CHAIN_TRACE=1: per-block timeline of the last chained pass (diagnostics)
     unsigned long long* chain_trace = nullptr;
     long long chain_trace_blocks = 0, chain_trace_last = 0;
@@ -254,6 +260,7 @@ MISOR_HIDDEN int tb_halo_depth(int T, int variant);
 MISOR_HIDDEN int tb_parts(const SweepParams& tp);
 
 // misor_solve.hip
+MISOR_HIDDEN bool lex_tiled_on(const misor_grid* g);
 MISOR_HIDDEN int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters,
                          double* res, bool* hand_off);
 

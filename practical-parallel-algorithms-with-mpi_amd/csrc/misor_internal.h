@@ -278,6 +278,29 @@ MISOR_DECL_TB(6) MISOR_DECL_TB(7) MISOR_DECL_TB(8) MISOR_DECL_TB(9) MISOR_DECL_T
 void launch_solve_lex(hipStream_t s, double* p, const double* rhs, int ni, int nj,
                       long long pitch, double idx2, double idy2, double factor, double cells,
                       int xorder, DevState* st);
+// what it keeps in LDS: 2 = p and rhs, 1 = p, 0 = nothing (p walked in HBM)
+int lex_use_lds(int ni, int nj);
+// the same solve as a tiled wavefront over the whole device (lex_tiled.hip):
+// tiles of tw x th cells, a persistent grid of at most wgs_cap workgroups
+// (<= 0: automatic); wk: its work area, kept by the grid between solves
+constexpr int kLexMinTile = 8;
+// default tile: 96 x 96 (runner-up 32 x 32; profiles/lex_tiled_ab.txt)
+constexpr int kLexTileW = 96, kLexTileH = 96;
+// automatic rule: tiled from this many interior cells on.  Measured against
+// the one-workgroup kernel (profiles/lex_tiled_ab.txt): 512^2 1.6-1.7x, 1024^2
+// 3.0-3.3x, 4096^2 14-16x faster, 256^2 0.8x (slower) -- so from the smallest
+// size measured faster, 512^2; below it the one-workgroup kernel stays
+constexpr long long kLexTiledCells = 512LL * 512;
+struct LexTiledWork {
+    void* buf = nullptr;
+    size_t bytes = 0;
+    int ntx = 0, nty = 0;  // the tile grid its order table lists
+};
+bool lex_tile_fits(int tw, int th);
+hipError_t launch_solve_lex_tiled(hipStream_t s, double* p, const double* rhs, int ni, int nj,
+                                  long long pitch, double idx2, double idy2, double factor,
+                                  double cells, int xorder, DevState* st, int tw, int th,
+                                  int wgs_cap, LexTiledWork& wk);
 // whole-solve single-workgroup kernel for grids whose p fits in LDS
 int small_solve_fits(int ni, int nj);
 void launch_solve_small(hipStream_t s, double* p, const double* rhs, int ni, int nj,

@@ -688,6 +688,16 @@ int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters,
     return MISOR_OK;
 }
 
+// would the next misor_solve_lex of this grid run the tiled wavefront
+// (MISOR_TUNE_LEX_TILED; automatic: p does not fit the one workgroup's LDS and
+// the grid has at least kLexTiledCells cells, the smallest size at which the
+// tiled kernel measured faster)
+bool lex_tiled_on(const misor_grid* g) {
+    if (g->lex_tiled >= 0) return g->lex_tiled == 1;
+    return lex_use_lds(g->loc.ni, g->loc.nj) == 0 &&
+           (long long)g->loc.ni * g->loc.nj >= kLexTiledCells;
+}
+
 int misor_solve_lex(misor_grid* g, int xorder, int* iters, double* res) {
     if (!g) return fail(MISOR_EINVAL, "null grid");
     if (g->desc.nranks != 1)
@@ -704,12 +714,25 @@ int misor_solve_lex(misor_grid* g, int xorder, int* iters, double* res) {
     HIPCHK(hipMemcpyAsync(g->st, g->st_host, sizeof(DevState), hipMemcpyHostToDevice,
                           g->stream));
     const double cells = (double)g->desc.imax * (double)g->desc.jmax;
-    launch_solve_lex(g->stream, pbuf(g, g->cur), g->fld[kRhs], g->loc.ni, g->loc.nj, g->pitch,
-                     g->sp.idx2, g->sp.idy2, g->sp.coef, cells, xorder != 0, g->st);
-    HIPCHK(hipGetLastError());
+    const bool tiled = lex_tiled_on(g);
+    if (tiled) {
+        HIPCHK(launch_solve_lex_tiled(g->stream, pbuf(g, g->cur), g->fld[kRhs], g->loc.ni,
+                                      g->loc.nj, g->pitch, g->sp.idx2, g->sp.idy2, g->sp.coef,
+                                      cells, xorder != 0, g->st, g->lex_tw ? g->lex_tw : kLexTileW,
+                                      g->lex_th ? g->lex_th : kLexTileH, g->lex_wgs,
+                                      g->lex_work));
+    } else {
+        launch_solve_lex(g->stream, pbuf(g, g->cur), g->fld[kRhs], g->loc.ni, g->loc.nj,
+                         g->pitch, g->sp.idx2, g->sp.idy2, g->sp.coef, cells, xorder != 0, g->st);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipMemcpyAsync(g->st_host, g->st, sizeof(DevState), hipMemcpyDeviceToHost,
                           g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
+    if (tiled && g->st_host->done != 1)  // a bounded wait of the wavefront gave up
+        return fail(MISOR_EHIP,
+                    "lexicographic wavefront stalled (a tile's wait ran into its limit); "
+                    "p is undefined");
     const int it = g->st_host->it;
     g->last_iters = it;
     g->stats.sweeps += it;
