@@ -135,7 +135,6 @@ void misor_destroy(misor_grid* g) {
     }
     if (g->ev_s) (void)hipEventDestroy(g->ev_s);
     if (g->ev_x) (void)hipEventDestroy(g->ev_x);
-    if (g->ev_d) (void)hipEventDestroy(g->ev_d);
     for (auto e : g->ev) (void)hipEventDestroy(e);
     for (auto& v : g->cev)
         for (auto e : v) (void)hipEventDestroy(e);
@@ -317,9 +316,8 @@ int misor_create(misor_grid** out, const misor_desc* d) {
         (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
         bool ok = hipStreamCreateWithPriority(&g->cstream, hipStreamNonBlocking, prio_hi) ==
                   hipSuccess;
-        for (hipEvent_t* e : {&g->ev_s, &g->ev_x, &g->ev_d, &g->ev_i[0], &g->ev_i[1],
-                              &g->ev_e2[0], &g->ev_e2[1],
-                              &g->ev_dk[0], &g->ev_dk[1]})
+        for (hipEvent_t* e : {&g->ev_s, &g->ev_x, &g->ev_i[0], &g->ev_i[1], &g->ev_e2[0],
+                              &g->ev_e2[1], &g->ev_dk[0], &g->ev_dk[1]})
             ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
         if (!ok) CREATE_FAIL(MISOR_EHIP, "comm stream/event creation failed");
         // blocks whose footprint (rows j0-2..j1+1, columns c0-2..c_end+1) stays clear
@@ -401,10 +399,7 @@ int misor_set_stream(misor_grid* g, void* s) {
 
 int misor_synchronize(misor_grid* g) {
     if (!g) return fail(MISOR_EINVAL, "null grid");
-    {
-        int rc_ = wait_stream(g, g->stream);
-        if (rc_) return rc_;
-    }
+    MISOR_TRY(wait_stream(g, g->stream));
     return MISOR_OK;
 }
 
@@ -536,10 +531,7 @@ int misor_gather(misor_grid* g, int field, double* host) {
         if (rc) return rc;
         HIPCHK(hipMemcpyAsync(g->red_host + 3, g->red_out + 3, sizeof(double),
                               hipMemcpyDeviceToHost, g->stream));
-        {
-            int rc_ = wait_stream(g, g->stream);
-            if (rc_) return rc_;
-        }
+        MISOR_TRY(wait_stream(g, g->stream));
         if (g->red_host[3] != 0.0)
             return fail(MISOR_ENOMEM, "gather: a rank could not allocate its %s buffer",
                         alloc_ok ? "peer's" : "own");
@@ -548,18 +540,12 @@ int misor_gather(misor_grid* g, int field, double* host) {
     const double* src = origin(g, const_cast<double*>(f)) + (long long)mine.j0 * g->pitch + mine.i0;
     HIPCHK(hipMemcpy2DAsync(g->gbuf, sizeof(double) * mine.w, src, sizeof(double) * g->pitch,
                             sizeof(double) * mine.w, mine.h, hipMemcpyDeviceToDevice, g->stream));
-    {
-        int rc_ = wait_stream(g, g->stream);
-        if (rc_) return rc_;
-    }
+    MISOR_TRY(wait_stream(g, g->stream));
     auto to_host = [&](const double* dev, const OwnedBlock& b) -> int {
         HIPCHK(hipMemcpy2DAsync(host + (size_t)b.gj0 * gw + b.gi0, sizeof(double) * gw, dev,
                                 sizeof(double) * b.w, sizeof(double) * b.w, b.h,
                                 hipMemcpyDeviceToHost, g->stream));
-        {
-            int rc_ = wait_stream(g, g->stream);
-            if (rc_) return rc_;
-        }
+        MISOR_TRY(wait_stream(g, g->stream));
         return MISOR_OK;
     };
     if (g->local) {
@@ -600,10 +586,7 @@ int misor_gather(misor_grid* g, int field, double* host) {
         }
     }
     if (rc) return rc;
-    {
-        int rc_ = wait_stream(g, g->stream);
-        if (rc_) return rc_;
-    }
+    MISOR_TRY(wait_stream(g, g->stream));
     return MISOR_OK;
 }
 

@@ -38,7 +38,15 @@ MISOR_HIDDEN int fail(int code, const char* fmt, ...) __attribute__((format(prin
                         __LINE__);                                                        \
     } while (0)
 
-#define NCCLCHK(x)                                                                        \
+// return the code of a failed call of the library's own (one that has
+// already recorded its message through fail)
+#define MISOR_TRY(x)           \
+    do {                       \
+        const int rc_ = (x);   \
+        if (rc_) return rc_;   \
+    } while (0)
+
+#define NCCLCHK(x)                                                                       \
     do {                                                                                  \
         ncclResult_t r_ = (x);                                                            \
         if (r_ != ncclSuccess)                                                            \
@@ -193,7 +201,7 @@ struct misor_grid {
     std::shared_ptr<LocalGroup> local;                   // in-process transport
     bool overlap = true;            // exchange on cstream while the interior sweeps
     hipStream_t cstream = nullptr;  // communication stream
-    hipEvent_t ev_s = nullptr, ev_x = nullptr, ev_d = nullptr;
+    hipEvent_t ev_s = nullptr, ev_x = nullptr;
     hipEvent_t ev_i[2] = {}, ev_dk[2] = {};  // interior blocks / decide of pass k, by k & 1
     hipEvent_t ev_e2[2] = {};                // edge blocks of pass k on cstream, by k & 1
 #ifdef MISOR_PROXY

@@ -82,7 +82,7 @@ constexpr TbVariant kTbVariants[] = {
     {0, 4, 2, kMaxT2, 0, 0}, {2, 2, 2, kMaxT2, 0, 0}, {13, 4, 2, kMaxT, 1, 1}};
 constexpr int kNumTbVariants = 14;
 constexpr int kHrTbVariant = 13;   // the skewed split ring (T = 1 unskewed)
-// the short plan of capped solves (misor_solve.hip solve_rb_from)
+// the short plan of capped solves (misor_solve.hip short_plan_on, pass_plan.h)
 constexpr int kShortTbVariant = kHrTbVariant;
 constexpr int kShortT = 10;
 constexpr long long kShortDistCells = 1LL << 28;  // decomposed: local blocks at least this big

@@ -101,10 +101,7 @@ int misor_max_uv(misor_grid* g, double* umax, double* vmax) {
     }
     HIPCHK(hipMemcpyAsync(g->red_host, g->red_out, 2 * sizeof(double), hipMemcpyDeviceToHost,
                           g->stream));
-    {
-        int rc_ = wait_stream(g, g->stream);
-        if (rc_) return rc_;
-    }
+    MISOR_TRY(wait_stream(g, g->stream));
     if (umax) *umax = g->red_host[0];
     if (vmax) *vmax = g->red_host[1];
     return MISOR_OK;
@@ -216,10 +213,7 @@ int misor_normalize_pressure(misor_grid* g) {
     }
     HIPCHK(hipMemcpyAsync(g->red_host, g->red_out, sizeof(double), hipMemcpyDeviceToHost,
                           g->stream));
-    {
-        int rc_ = wait_stream(g, g->stream);
-        if (rc_) return rc_;
-    }
+    MISOR_TRY(wait_stream(g, g->stream));
     const double mx = g->red_host[0];
     int E = 0;
     (void)frexp(mx, &E);
@@ -234,10 +228,7 @@ int misor_normalize_pressure(misor_grid* g) {
     }
     HIPCHK(hipMemcpyAsync(g->red_host, g->red_out, 3 * sizeof(double), hipMemcpyDeviceToHost,
                           g->stream));
-    {
-        int rc_ = wait_stream(g, g->stream);
-        if (rc_) return rc_;
-    }
+    MISOR_TRY(wait_stream(g, g->stream));
     const double cells = (double)(g->desc.imax + 2) * (double)(g->desc.jmax + 2);
     const double avg = exact_sum_value(g->red_host, E) / cells;  // solver.c:213
     timed = ns_pair(g, 2, false, &t0, &t1);

@@ -414,7 +414,7 @@ int configure_tb(misor_grid* g, int T, int variant, int rows) {
     }
     tb_geometry(g, std::max(2, Te), tp);
     g->tb_nparts = tb_parts(tp);
-    // The short plan (solve_rb_from): a single-rank solve capped at few
+    // The short plan (misor_solve.hip short_plan_on): a solve capped at few
     // iterations runs them in fewer, longer passes of the split-ring kernel
     // when that saves a pass; its geometries share the partials
     // Where (round 5, the chained split ring; profiles/r05_plan_ab*.txt, wall
@@ -426,7 +426,7 @@ int configure_tb(misor_grid* g, int T, int variant, int rows) {
     //    at 100 iterations, 20 iterations in 2 passes instead of 3): the same;
     //  - a single rank of 2^28 cells, and decomposed blocks of >= 2^28 (the
     //    two- and four-GPU splits of the bench grid): only where it saves
-    //    passes, the rule in solve_rb_from (at 100 iterations the two plans are
+    //    passes, pass_plan.h short_plan_saves_passes (at 100 iterations the two plans are
     //    within 1-3%; the 4-GPU rank block through the pipelined loop of round
     //    5, 20 iterations: 0.2247-0.2250 vs 0.2317-0.2327 ms per iteration,
     //    profiles/r05_plan_ab_ranks.txt -- round 4's loop measured the opposite).

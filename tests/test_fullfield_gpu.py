@@ -5,7 +5,7 @@ Config 4 (2D Poisson red-black SOR, 32768^2, bench.py --steps 20 --warmup 5,
 the driver's setting, BENCH_r04.json): the bench runs a warm-up solve of 5
 iterations and one of 20, then times a third solve of 20 iterations (the short
 pass plan: two 10-iteration passes of the split-ring kernel, TB variant 13,
-misor_api.hip solve_rb_from).  The test replays exactly that sequence on one
+misor_solve.hip short_plan_on).  The test replays exactly that sequence on one
 Grid, asserts that the timed solve ran that kernel and plan, downloads the field the timed solve starts from, and
 checks the WHOLE 32770^2 result (ghosts included) bit for bit, and res to
 1e-12, against the multi-core restatement of solveRB

@@ -2,12 +2,15 @@
 the reference's failure mode is fail-fast; here memory errors, leaks and UB
 in the CPU-side code are caught by a sanitized build).
 
-Two executables, built by `make asan` (gcc -fsanitize=address,undefined
+Three executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
 -fno-sanitize-recover=undefined):
   * bin/asan/host-check (practical-parallel-algorithms-with-mpi_amd/host/
     sanitize_main.c): the .par reader on every .par the tests use, the
     RCCL-id hand-off file (right tag taken, stale tag refused), the legacy
     VTK writer in both formats;
+  * bin/asan/pass-plan-check (host/pass_plan_check.cc): the pass-plan
+    arithmetic of the red-black solve loop (csrc/pass_plan.h), every plan of
+    1..400 iterations in passes of 1..10, and the short plan's rule;
   * oracle/_asan/oracle-check (oracle/sanitize_main.c): every oracle
     function on small ragged grids, with the reference's iteration KATs and
     multi-threaded == scalar bit identity.
@@ -42,6 +45,12 @@ def test_host_code_sanitized(tmp_path):
     out = run([os.path.join(PKG, "bin", "asan", "host-check"), str(tmp_path)] + pars)
     assert "all checks passed" in out
     assert (tmp_path / "sanitize_ascii.vtk").stat().st_size > 0
+
+
+def test_pass_plan_sanitized():
+    build(PKG)
+    out = run([os.path.join(PKG, "bin", "asan", "pass-plan-check")])
+    assert "all checks passed" in out
 
 
 def test_oracle_sanitized():
