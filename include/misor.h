@@ -421,6 +421,49 @@ int misor3_set_tuning(misor_grid3* g, int key, int value);
 int misor3_get_tuning(const misor_grid3* g, int key, int* value);
 int misor3_get_solve_time(const misor_grid3* g, double* ms, long long* iters);
 
+/* --- the box over a 3D Cartesian process grid (assignment-6/src/comm.c:24-101,
+ * 476-513), a second decomposition beside the slabs.  A rank owns a block of
+ * {ni, nj, nk} cells; its local array is the reference's, (ni+2)(nj+2)(nk+2)
+ * doubles, whose one ghost layer is the 1-deep halo on the sides that face
+ * another rank. */
+typedef struct {
+    int n[3];            /* local interior cells {ni, nj, nk} */
+    int off[3];          /* global index of local cell 0 per axis (as koff) */
+    int coords[3], dims[3];            /* {x, y, z} */
+    int neighbours[6];   /* left, right, bottom, top, front, back rank or -1
+                          * (the reference's Direction order, comm.h:20) */
+} misor3_local;
+
+/* MPI_Dims_create(nranks, 3) + sizeOfRank per axis.  Entries of dims_in that
+ * are 0 (or dims_in == NULL) are filled with the most balanced factorisation,
+ * the largest factor to z, then y, then x (the reference indexes its dims
+ * KDIM = 0, JDIM = 1, IDIM = 2); non-zero entries are kept, and a product
+ * that is not nranks (with zeros left: does not divide it) is MISOR_EINVAL.  rank = (cz*dims[1] + cy)*dims[0] + cx
+ * (MPI_Cart_create without reorder, z slowest).  Every rank owns at least 2
+ * cells per axis.  host-only */
+int misor3_decompose_cart(int nranks, int rank, const int dims_in[3],
+                          int imax, int jmax, int kmax, misor3_local* out);
+/* as misor3_create, on the process grid dims {x, y, z} ({0,0,0} or NULL:
+ * automatic); nranks <= 1 is misor3_create.  On such a grid
+ *  - upload / download / fill move the rank's local array, gather assembles
+ *    the global field on rank 0 (owned cells plus the ghost cells on each
+ *    rank's physical sides), misor3_local_info reports nk and off[2];
+ *  - misor3_solve is the reference's own loop (solver.c:199-291): exchange p,
+ *    colour pass 0, exchange p, colour pass 1, all-reduce and test.  p and the
+ *    iteration count are those of the single-domain solve.  The solve ends
+ *    with one more exchange, so p's halo holds the neighbours' final values
+ *    when misor3_adapt_uvw or misor3_download reads it;
+ *  - MISOR3_TUNE_SWEEP reads 0; setting it or MISOR3_TUNE_RESIDENT to 1 is
+ *    MISOR_EINVAL; the other knobs are accepted and ignored. */
+int misor3_create_cart(misor_grid3** out, const misor3_desc* d, const int dims[3]);
+int misor3_local_info_cart(const misor_grid3* g, misor3_local* out);
+/* the reference's commExchange, collective: the 1-deep halo of `field` on the
+ * sides that face another rank, axis by axis (x, then y, then z), each face
+ * spanning the ghost layers already filled -- so the block's edge and corner
+ * ghosts arrive too.  Ghost cells on physical sides are not touched.  A no-op
+ * on one rank; MISOR_ESTATE on a slab grid */
+int misor3_exchange(misor_grid3* g, int field);
+
 #ifdef __cplusplus
 }
 #endif

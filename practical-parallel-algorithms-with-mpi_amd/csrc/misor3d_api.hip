@@ -15,6 +15,18 @@
 // Storage per field: planes -1 .. K+2 of the rank's slab (K = its plane count),
 // i.e. the reference's local array (planes 0 .. K+1) plus one more plane on
 // each side for the 2-deep halo the fused sweep reads.
+//
+// Second decomposition (misor3_create_cart): the reference's 3D Cartesian
+// process grid itself.  A rank holds a block of ni x nj x nk cells as the
+// reference's local array (ni+2)(nj+2)(nk+2), whose one ghost layer is the
+// 1-deep halo; the allocation keeps the two spare planes -1 and K+2 of the
+// slab storage (unused here), so plane_ptr, kSlack, fill and the gather treat
+// both kinds of grid alike.  Halos move axis by axis -- x, y, z, each face
+// spanning the ghost layers already filled, so edges and corners need no
+// messages of their own: x and y faces through pack / unpack kernels and
+// staging buffers (halo3.hip), z faces as whole planes straight from the
+// field.  The solve on such a grid is the reference's two colour passes with
+// an exchange before each.
 
 #include <cmath>
 #include <condition_variable>
@@ -111,6 +123,13 @@ struct misor_grid3 {
     ncclComm_t comm = nullptr;
     std::shared_ptr<LocalGroup3> local;
     double* gstage = nullptr;     // rank 0: receive staging of misor3_gather (RCCL)
+    // Cartesian process grid (misor3_create_cart)
+    bool cart = false;
+    misor3_local loc{};
+    double* hbuf = nullptr;       // staging of the x / y faces, one allocation
+    double* hsend[4] = {};        // left, right, bottom, top: packed owned layer
+    double* hrecv[4] = {};        // the neighbour's, before it is unpacked into the ghost layer
+    double* gbuf = nullptr;       // the box this rank contributes to misor3_gather
 };
 
 namespace {
@@ -212,6 +231,203 @@ int allreduce3(misor_grid3* g, double* dev, int n, bool is_max) {
     return MISOR_OK;
 }
 
+// ------------------------------------------------ Cartesian process grid
+// sides in the reference's Direction order: 0 left, 1 right, 2 bottom, 3 top,
+// 4 front, 5 back; side s lies on axis s / 2, its opposite is s ^ 1
+
+// the x or y face of side s (0..3), ghost rims of the other two axes included:
+// the ghost layer (halo) or the owned layer next to it
+Box3 face_box(const misor_grid3* g, int s, bool halo) {
+    const G3& G = g->g;
+    Box3 b{0, 0, 0, G.I + 2, G.J + 2, G.K + 2, G.sx, G.sxy};
+    const int n = s < 2 ? G.I : G.J;
+    const int layer = (s & 1) ? (halo ? n + 1 : n) : (halo ? 0 : 1);
+    if (s < 2) {
+        b.x0 = layer;
+        b.nx = 1;
+    } else {
+        b.y0 = layer;
+        b.ny = 1;
+    }
+    return b;
+}
+
+// what a rank contributes to the global array: its owned cells plus the ghost
+// layer on its physical sides (with the physical edges and corners it holds);
+// these boxes tile the global array exactly once
+Box3 own_box(const misor3_local& L) {
+    Box3 b;
+    int lo[3], cnt[3];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = L.neighbours[2 * a] < 0 ? 0 : 1;
+        const int hi = L.neighbours[2 * a + 1] < 0 ? L.n[a] + 1 : L.n[a];
+        cnt[a] = hi - lo[a] + 1;
+    }
+    b.x0 = lo[0], b.y0 = lo[1], b.z0 = lo[2];
+    b.nx = cnt[0], b.ny = cnt[1], b.nz = cnt[2];
+    b.sx = L.n[0] + 2;
+    b.sxy = (long long)(L.n[0] + 2) * (L.n[1] + 2);
+    return b;
+}
+
+// the 1-deep halo of buffer b along one axis, both directions
+int exchange_cart_axis(misor_grid3* g, int b, int axis) {
+    const int* nb = g->loc.neighbours;
+    const int s0 = 2 * axis, K = g->g.K;
+    const size_t plane = (size_t)g->g.sxy;
+    double* f = g->fld[b];
+    if (axis < 2) {
+        for (int s = s0; s < s0 + 2; ++s)
+            if (nb[s] >= 0) launch3_box_pack(g->stream, f, face_box(g, s, false), g->hsend[s]);
+        HIPCHK3(hipGetLastError());
+    }
+    if (g->local) {
+        LocalGroup3& G = *g->local;
+        HIPCHK3(hipStreamSynchronize(g->stream));
+        G.barrier();  // every rank's send buffers / sent planes are final
+        for (int s = s0; s < s0 + 2; ++s) {
+            if (nb[s] < 0) continue;
+            misor_grid3* q = G.members[nb[s]];
+            if (axis < 2) {
+                HIPCHK3(hipMemcpyAsync(g->hrecv[s], q->hsend[s ^ 1],
+                                       sizeof(double) * (size_t)face_box(g, s, true).cells(),
+                                       hipMemcpyDeviceToDevice, g->stream));
+            } else {  // front: the neighbour's plane K to plane 0; back: its plane 1 to K+1
+                HIPCHK3(hipMemcpyAsync(plane_ptr(g, b, s == 4 ? 0 : K + 1),
+                                       plane_ptr(q, b, s == 4 ? q->g.K : 1),
+                                       sizeof(double) * plane, hipMemcpyDeviceToDevice,
+                                       g->stream));
+            }
+        }
+    } else {
+        NCCLCHK3(ncclGroupStart());
+        for (int s = s0; s < s0 + 2; ++s) {
+            if (nb[s] < 0) continue;
+            if (axis < 2) {
+                const size_t cnt = (size_t)face_box(g, s, true).cells();
+                NCCLCHK3(ncclSend(g->hsend[s], cnt, ncclDouble, nb[s], g->comm, g->stream));
+                NCCLCHK3(ncclRecv(g->hrecv[s], cnt, ncclDouble, nb[s], g->comm, g->stream));
+            } else {
+                NCCLCHK3(ncclSend(plane_ptr(g, b, s == 4 ? 1 : K), plane, ncclDouble, nb[s],
+                                  g->comm, g->stream));
+                NCCLCHK3(ncclRecv(plane_ptr(g, b, s == 4 ? 0 : K + 1), plane, ncclDouble, nb[s],
+                                  g->comm, g->stream));
+            }
+        }
+        NCCLCHK3(ncclGroupEnd());
+    }
+    if (axis < 2) {
+        for (int s = s0; s < s0 + 2; ++s)
+            if (nb[s] >= 0) launch3_box_unpack(g->stream, f, face_box(g, s, true), g->hrecv[s]);
+        HIPCHK3(hipGetLastError());
+    }
+    if (g->local) {
+        HIPCHK3(hipStreamSynchronize(g->stream));
+        g->local->barrier();  // nobody repacks a buffer or overwrites a plane being copied
+    }
+    return MISOR_OK;
+}
+
+// the halo of buffer b on the axes of `axes` (bit 0 x, 1 y, 2 z), in that
+// order; an axis the process grid does not cut is skipped by every rank alike
+int exchange_cart(misor_grid3* g, int b, int axes) {
+    if (!dist(g)) return MISOR_OK;
+    for (int a = 0; a < 3; ++a)
+        if (((axes >> a) & 1) && g->loc.dims[a] > 1) {
+            const int rc = exchange_cart_axis(g, b, a);
+            if (rc != MISOR_OK) return rc;
+        }
+    return MISOR_OK;
+}
+
+// host: one rank's packed box into the global array
+void scatter_box(const misor3_local& L, const Box3& bx, const double* packed, const misor3_desc& d,
+                 double* global) {
+    const long long SX = d.imax + 2, SXY = SX * (d.jmax + 2);
+    for (int z = 0; z < bx.nz; ++z)
+        for (int y = 0; y < bx.ny; ++y)
+            memcpy(global + (long long)(L.off[2] + bx.z0 + z) * SXY +
+                       (long long)(L.off[1] + bx.y0 + y) * SX + (L.off[0] + bx.x0),
+                   packed + ((long long)z * bx.ny + y) * bx.nx, sizeof(double) * (size_t)bx.nx);
+}
+
+int gather_cart(misor_grid3* g, int field, double* host_global) {
+    const Box3 mine = own_box(g->loc);
+    if (!g->gbuf)
+        HIPCHK3(hipMalloc(&g->gbuf, sizeof(double) * (size_t)g->n));
+    launch3_box_pack(g->stream, g->fld[field], mine, g->gbuf);
+    HIPCHK3(hipGetLastError());
+    std::vector<double> stage;
+    auto rank_box = [&](int r, misor3_local& L) {
+        misor3_decompose_cart(g->nranks, r, g->loc.dims, g->desc.imax, g->desc.jmax, g->desc.kmax,
+                              &L);
+        return own_box(L);
+    };
+    if (g->local) {
+        LocalGroup3& G = *g->local;
+        HIPCHK3(hipStreamSynchronize(g->stream));
+        G.barrier();  // every rank's box is packed
+        if (g->rank == 0) {
+            for (int r = 0; r < g->nranks; ++r) {
+                misor3_local L;
+                const Box3 bx = rank_box(r, L);
+                misor_grid3* q = G.members[r];
+                stage.resize((size_t)bx.cells());
+                HIPCHK3(hipSetDevice(q->device));
+                HIPCHK3(hipMemcpy(stage.data(), q->gbuf, sizeof(double) * stage.size(),
+                                  hipMemcpyDeviceToHost));
+                scatter_box(L, bx, stage.data(), g->desc, host_global);
+            }
+            HIPCHK3(hipSetDevice(g->device));
+        }
+        G.barrier();
+        return MISOR_OK;
+    }
+    if (g->rank != 0) {
+        NCCLCHK3(ncclSend(g->gbuf, (size_t)mine.cells(), ncclDouble, 0, g->comm, g->stream));
+        HIPCHK3(hipStreamSynchronize(g->stream));
+        return MISOR_OK;
+    }
+    // rank 0 holds the largest block (sizeOfRank), so its local array bounds every box
+    if (!g->gstage) HIPCHK3(hipMalloc(&g->gstage, sizeof(double) * (size_t)g->n));
+    for (int r = 0; r < g->nranks; ++r) {
+        misor3_local L;
+        const Box3 bx = rank_box(r, L);
+        stage.resize((size_t)bx.cells());
+        const double* src = g->gbuf;
+        if (r != 0) {
+            NCCLCHK3(ncclRecv(g->gstage, stage.size(), ncclDouble, r, g->comm, g->stream));
+            src = g->gstage;
+        }
+        HIPCHK3(hipMemcpyAsync(stage.data(), src, sizeof(double) * stage.size(),
+                               hipMemcpyDeviceToHost, g->stream));
+        HIPCHK3(hipStreamSynchronize(g->stream));
+        scatter_box(L, bx, stage.data(), g->desc, host_global);
+    }
+    return MISOR_OK;
+}
+
+// most balanced factorisation of m into three factors f[0] >= f[1] >= f[2], of
+// which the last 3 - k are 1: the smallest largest factor, then the smallest
+// second one (MPI_Dims_create's rule); false if there is none
+bool balanced_factors(int m, int k, int f[3]) {
+    bool found = false;
+    for (int a = 1; a <= m; ++a) {
+        if (m % a) continue;
+        for (int b = 1; b <= a; ++b) {
+            if ((m / a) % b) continue;
+            const int c = m / a / b;
+            if (c > b) continue;
+            if ((k < 3 && c != 1) || (k < 2 && b != 1) || (k < 1 && a != 1)) continue;
+            if (!found) {  // a ascends, then b: the first hit is the lexicographic minimum
+                f[0] = a, f[1] = b, f[2] = c;
+                found = true;
+            }
+        }
+    }
+    return found;
+}
+
 }  // namespace
 
 extern "C" {
@@ -231,6 +447,8 @@ void misor3_destroy(misor_grid3* g) {
     (void)hipFree(g->st2);
     (void)hipHostFree(g->st_host);
     (void)hipFree(g->gstage);
+    (void)hipFree(g->hbuf);
+    (void)hipFree(g->gbuf);
     for (auto& e : g->ev)
         if (e) (void)hipEventDestroy(e);
     if (g->comm) ncclCommDestroy(g->comm);
@@ -251,25 +469,74 @@ int misor3_decompose(int nranks, int rank, int kmax, int* kloc, int* koff) {
     return MISOR_OK;
 }
 
-int misor3_create(misor_grid3** out, const misor3_desc* d) {
+int misor3_decompose_cart(int nranks, int rank, const int dims_in[3], int imax, int jmax,
+                          int kmax, misor3_local* out) {
+    if (!out) return fail3(MISOR_EINVAL, "null argument");
+    if (nranks < 1 || rank < 0 || rank >= nranks)
+        return fail3(MISOR_EINVAL, "bad rank %d of %d", rank, nranks);
+    int d[3] = {0, 0, 0};
+    int fixed = 1, nfree = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (dims_in) d[a] = dims_in[a];
+        if (d[a] < 0) return fail3(MISOR_EINVAL, "negative process-grid entry %d", d[a]);
+        if (d[a] > 0 && fixed <= nranks) fixed *= d[a];  // (stops growing once it is too big)
+        if (d[a] == 0) ++nfree;
+    }
+    int f[3];
+    if (nranks % fixed || !balanced_factors(nranks / fixed, nfree, f))
+        return fail3(MISOR_EINVAL, "process grid %dx%dx%d does not hold %d ranks", d[0], d[1],
+                     d[2], nranks);
+    for (int a = 2, q = 0; a >= 0; --a)  // the largest free factor to z, then y, then x
+        if (d[a] == 0) d[a] = f[q++];
+    const int N[3] = {imax, jmax, kmax};
+    for (int a = 0; a < 3; ++a)
+        if (N[a] / d[a] < 2)
+            return fail3(MISOR_EINVAL, "%d cells along %c over %d ranks: fewer than 2 per rank",
+                         N[a], "xyz"[a], d[a]);
+    const int c[3] = {rank % d[0], (rank / d[0]) % d[1], rank / (d[0] * d[1])};
+    const int step[3] = {1, d[0], d[0] * d[1]};
+    for (int a = 0; a < 3; ++a) {
+        out->dims[a] = d[a];
+        out->coords[a] = c[a];
+        out->n[a] = size_of_rank3(c[a], d[a], N[a]);
+        out->off[a] = 0;
+        for (int r = 0; r < c[a]; ++r) out->off[a] += size_of_rank3(r, d[a], N[a]);
+        out->neighbours[2 * a] = c[a] > 0 ? rank - step[a] : -1;
+        out->neighbours[2 * a + 1] = c[a] < d[a] - 1 ? rank + step[a] : -1;
+    }
+    return MISOR_OK;
+}
+
+// misor3_create (dims == nullptr: slabs) and misor3_create_cart
+static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, bool cart) {
     if (!out || !d) return fail3(MISOR_EINVAL, "null argument");
     *out = nullptr;
     if (d->imax < 2 || d->jmax < 2 || d->kmax < 2)
         return fail3(MISOR_EINVAL, "imax, jmax, kmax must be >= 2");
     const int nranks = d->nranks > 0 ? d->nranks : 1;
+    if (nranks <= 1) cart = false;
     int kloc = d->kmax, koff = 0;
+    misor3_local loc{};
     if (nranks > 1) {
         if (!d->comm_id) return fail3(MISOR_EINVAL, "nranks > 1 needs a comm_id");
-        const int rc = misor3_decompose(nranks, d->rank, d->kmax, &kloc, &koff);
+        const int rc = cart ? misor3_decompose_cart(nranks, d->rank, dims, d->imax, d->jmax,
+                                                    d->kmax, &loc)
+                            : misor3_decompose(nranks, d->rank, d->kmax, &kloc, &koff);
         if (rc != MISOR_OK) return rc;
     }
+    const int iloc = cart ? loc.n[0] : d->imax, jloc = cart ? loc.n[1] : d->jmax;
+    if (cart) kloc = loc.n[2], koff = loc.off[2];
     misor_grid3* g = new misor_grid3();
     g->desc = *d;
     g->device = d->device;
     g->nranks = nranks;
     g->rank = nranks > 1 ? d->rank : 0;
-    g->prev = g->rank > 0 ? g->rank - 1 : -1;
-    g->next = g->rank < nranks - 1 ? g->rank + 1 : -1;
+    g->cart = cart;
+    g->loc = loc;
+    if (!cart) {
+        g->prev = g->rank > 0 ? g->rank - 1 : -1;
+        g->next = g->rank < nranks - 1 ? g->rank + 1 : -1;
+    }
     if (d->device >= 0) {
         if (hipSetDevice(d->device) != hipSuccess) {
             delete g;
@@ -286,15 +553,29 @@ int misor3_create(misor_grid3** out, const misor3_desc* d) {
     } while (0)
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess)
         CF(MISOR_EHIP, "hipStreamCreate failed");
-    g->g.I = d->imax;
-    g->g.J = d->jmax;
+    g->g.I = iloc;
+    g->g.J = jloc;
     g->g.K = kloc;
-    g->g.sx = d->imax + 2;
-    g->g.sxy = (long long)(d->imax + 2) * (d->jmax + 2);
+    g->g.sx = iloc + 2;
+    g->g.sxy = (long long)(iloc + 2) * (jloc + 2);
     g->g.Kg = d->kmax;
     g->g.koff = koff;
     g->g.lo_phys = g->prev < 0;
     g->g.hi_phys = g->next < 0;
+    g->g.Ig = d->imax;
+    g->g.Jg = d->jmax;
+    if (cart) {
+        g->g.ioff = loc.off[0];
+        g->g.joff = loc.off[1];
+        g->g.xlo_phys = loc.neighbours[0] < 0;
+        g->g.xhi_phys = loc.neighbours[1] < 0;
+        g->g.ylo_phys = loc.neighbours[2] < 0;
+        g->g.yhi_phys = loc.neighbours[3] < 0;
+        g->g.lo_phys = loc.neighbours[4] < 0;
+        g->g.hi_phys = loc.neighbours[5] < 0;
+        g->sweep = 0;     // the solve is the two colour passes
+        g->resident = 0;
+    }
     g->n = g->g.sxy * (kloc + 2);
     g->nalloc = g->g.sxy * (kloc + 2 * kHalo);
     // initSolver, solver.c:86-95
@@ -327,6 +608,20 @@ int misor3_create(misor_grid3** out, const misor3_desc* d) {
         hipMalloc(&g->st2, sizeof(DevState)) != hipSuccess ||
         hipHostMalloc(&g->st_host, sizeof(DevState), hipHostMallocDefault) != hipSuccess)
         CF(MISOR_ENOMEM, "allocation failed");
+    if (cart) {
+        // a send and a receive buffer per x / y side, each the size of its face
+        // with the ghost rims: (nj+2)(nk+2) and (ni+2)(nk+2) doubles
+        const size_t fx = (size_t)(jloc + 2) * (kloc + 2), fy = (size_t)(iloc + 2) * (kloc + 2);
+        if (hipMalloc(&g->hbuf, sizeof(double) * 4 * (fx + fy)) != hipSuccess)
+            CF(MISOR_ENOMEM, "allocation of the halo buffers failed");
+        double* b = g->hbuf;
+        for (int s = 0; s < 4; ++s) {
+            const size_t f = s < 2 ? fx : fy;
+            g->hsend[s] = b;
+            g->hrecv[s] = b + f;
+            b += 2 * f;
+        }
+    }
     if (nranks > 1) {
         if (memcmp(d->comm_id, kLocalPrefix3, sizeof kLocalPrefix3 - 1) == 0) {
             char name[MISOR_COMM_ID_BYTES + 1];
@@ -361,11 +656,42 @@ int misor3_create(misor_grid3** out, const misor3_desc* d) {
     return MISOR_OK;
 }
 
+int misor3_create(misor_grid3** out, const misor3_desc* d) {
+    return create3(out, d, nullptr, false);
+}
+
+int misor3_create_cart(misor_grid3** out, const misor3_desc* d, const int dims[3]) {
+    return create3(out, d, dims, true);
+}
+
 int misor3_local_info(const misor_grid3* g, int* kloc, int* koff) {
     if (!g) return fail3(MISOR_EINVAL, "null grid");
     if (kloc) *kloc = g->g.K;
     if (koff) *koff = g->g.koff;
     return MISOR_OK;
+}
+
+// one rank and slabs too: the block they hold on a 1 x 1 x nranks process grid
+int misor3_local_info_cart(const misor_grid3* g, misor3_local* out) {
+    if (!g || !out) return fail3(MISOR_EINVAL, "null argument");
+    if (g->cart) {
+        *out = g->loc;
+        return MISOR_OK;
+    }
+    *out = misor3_local{{g->g.I, g->g.J, g->g.K}, {0, 0, g->g.koff}, {0, 0, g->rank},
+                        {1, 1, g->nranks}, {-1, -1, -1, -1, g->prev, g->next}};
+    return MISOR_OK;
+}
+
+static double* fld3(misor_grid3* g, int field);
+
+int misor3_exchange(misor_grid3* g, int field) {
+    if (!g || !fld3(g, field)) return fail3(MISOR_EINVAL, "bad exchange");
+    HIPCHK3(hipSetDevice(g->device));
+    if (!dist(g)) return MISOR_OK;
+    if (!g->cart)
+        return fail3(MISOR_ESTATE, "misor3_exchange needs a Cartesian grid (misor3_create_cart)");
+    return exchange_cart(g, field, 7);
 }
 
 static double* fld3(misor_grid3* g, int field) {
@@ -399,6 +725,7 @@ int misor3_gather(misor_grid3* g, int field, double* host_global) {
     if (g->rank == 0 && !host_global) return fail3(MISOR_EINVAL, "rank 0 needs a buffer");
     HIPCHK3(hipSetDevice(g->device));
     if (!dist(g)) return misor3_download(g, field, host_global);
+    if (g->cart) return gather_cart(g, field, host_global);
     const long long sxy = g->g.sxy;
     auto range = [&](int r, int& k_first, int& k_count, long long& goff) {
         int kl = 0, ko = 0;
@@ -473,9 +800,13 @@ int misor3_set_dt(misor_grid3* g, double dt) {
 static int absmax_uvw(misor_grid3* g) {
     const int k_first = g->g.lo_phys ? 0 : 1, k_last = g->g.hi_phys ? g->g.K + 1 : g->g.K;
     const long long off = (long long)k_first * g->g.sxy;
-    launch3_absmax(g->stream, g->fld[MISOR3_U] + off, g->fld[MISOR3_V] + off,
-                   g->fld[MISOR3_W] + off, (long long)(k_last - k_first + 1) * g->g.sxy,
-                   g->partials, g->out);
+    if (g->cart)  // owned cells and physical ghosts: no stale halo copy enters the maximum
+        launch3_absmax_box(g->stream, g->fld[MISOR3_U], g->fld[MISOR3_V], g->fld[MISOR3_W],
+                           own_box(g->loc), g->partials, g->out);
+    else
+        launch3_absmax(g->stream, g->fld[MISOR3_U] + off, g->fld[MISOR3_V] + off,
+                       g->fld[MISOR3_W] + off, (long long)(k_last - k_first + 1) * g->g.sxy,
+                       g->partials, g->out);
     HIPCHK3(hipGetLastError());
     int rc = allreduce3(g, g->out, 3, true);
     if (rc != MISOR_OK) return rc;
@@ -519,10 +850,11 @@ int misor3_set_boundary_conditions(misor_grid3* g) {
     const int I = g->g.I, J = g->g.J, K = g->g.K;
     double *u = g->fld[MISOR3_U], *v = g->fld[MISOR3_V], *w = g->fld[MISOR3_W];
     const misor3_desc& d = g->desc;
-    launch3_wall(g->stream, g->g, v, u, w, 1, J + 1, J, J, J - 1, d.bcTop);
-    launch3_wall(g->stream, g->g, v, u, w, 1, 0, 1, 0, 1, d.bcBottom);
-    launch3_wall(g->stream, g->g, u, v, w, 0, 0, 1, 0, 1, d.bcLeft);
-    launch3_wall(g->stream, g->g, u, v, w, 0, I + 1, I, I, I - 1, d.bcRight);
+    // (a Cartesian block: only the walls on its physical sides, over its own cells)
+    if (g->g.yhi_phys) launch3_wall(g->stream, g->g, v, u, w, 1, J + 1, J, J, J - 1, d.bcTop);
+    if (g->g.ylo_phys) launch3_wall(g->stream, g->g, v, u, w, 1, 0, 1, 0, 1, d.bcBottom);
+    if (g->g.xlo_phys) launch3_wall(g->stream, g->g, u, v, w, 0, 0, 1, 0, 1, d.bcLeft);
+    if (g->g.xhi_phys) launch3_wall(g->stream, g->g, u, v, w, 0, I + 1, I, I, I - 1, d.bcRight);
     if (g->g.lo_phys) launch3_wall(g->stream, g->g, w, u, v, 2, 0, 1, 0, 1, d.bcFront);
     if (g->g.hi_phys) launch3_wall(g->stream, g->g, w, u, v, 2, K + 1, K, K, K - 1, d.bcBack);
     HIPCHK3(hipGetLastError());
@@ -542,8 +874,9 @@ int misor3_set_special_boundary_condition(misor_grid3* g) {
 int misor3_compute_fg(misor_grid3* g) {
     if (!g) return fail3(MISOR_EINVAL, "null grid");
     HIPCHK3(hipSetDevice(g->device));
+    // (a Cartesian block: with the edge ghosts k3_fg reads, u[q-X+Y] and the like)
     for (int b : {MISOR3_U, MISOR3_V, MISOR3_W}) {
-        int rc = exchange3(g, b, 1);
+        int rc = g->cart ? exchange_cart(g, b, 7) : exchange3(g, b, 1);
         if (rc != MISOR_OK) return rc;
     }
     const misor3_desc& d = g->desc;
@@ -567,7 +900,14 @@ int misor3_compute_fg(misor_grid3* g) {
 int misor3_compute_rhs(misor_grid3* g) {
     if (!g) return fail3(MISOR_EINVAL, "null grid");
     HIPCHK3(hipSetDevice(g->device));
-    int rc = exchange3(g, MISOR3_H, 1);
+    int rc;
+    if (g->cart) {  // f(0,j,k), g(i,0,k), h(i,j,0) next to a rank: f along x, g along y, h along z
+        if ((rc = exchange_cart(g, MISOR3_F, 1)) != MISOR_OK) return rc;
+        if ((rc = exchange_cart(g, MISOR3_G, 2)) != MISOR_OK) return rc;
+        rc = exchange_cart(g, MISOR3_H, 4);
+    } else {
+        rc = exchange3(g, MISOR3_H, 1);
+    }
     if (rc != MISOR_OK) return rc;
     launch3_rhs(g->stream, g->g, g->fld[MISOR3_F], g->fld[MISOR3_G], g->fld[MISOR3_H],
                 g->fld[MISOR3_RHS], 1.0 / g->dx, 1.0 / g->dy, 1.0 / g->dz, 1.0 / g->dt);
@@ -588,7 +928,7 @@ int misor3_adapt_uvw(misor_grid3* g) {
 int misor3_normalize_pressure(misor_grid3* g) {
     if (!g) return fail3(MISOR_EINVAL, "null grid");
     HIPCHK3(hipSetDevice(g->device));
-    const double cells = (double)((long long)g->g.I * g->g.J * g->desc.kmax);
+    const double cells = (double)((long long)g->desc.imax * g->desc.jmax * g->desc.kmax);
     if (!dist(g)) {
         launch3_normalize(g->stream, g->g, g->fld[MISOR3_P], g->partials, g->out, cells);
     } else {
@@ -631,7 +971,7 @@ int misor3_solve(misor_grid3* g, int* iters, double* res) {
     const misor3_desc& d = g->desc;
     const double dx2 = g->dx * g->dx, dy2 = g->dy * g->dy, dz2 = g->dz * g->dz;
     const double factor = d.omega * 0.5 * (dx2 * dy2 * dz2) / (dy2 * dz2 + dx2 * dz2 + dx2 * dy2);
-    const double cells = (double)((long long)g->g.I * g->g.J * d.kmax);
+    const double cells = (double)((long long)d.imax * d.jmax * d.kmax);
     DevState s0{};
     s0.res = 1.0;
     s0.epssq = d.eps * d.eps;
@@ -640,6 +980,48 @@ int misor3_solve(misor_grid3* g, int* iters, double* res) {
     if (s0.done) {
         if (iters) *iters = 0;
         if (res) *res = 1.0;
+        return MISOR_OK;
+    }
+    if (g->cart) {
+        // A Cartesian block: the reference's own loop (solver.c:199-291) -- exchange
+        // p, colour pass 0, exchange p, colour pass 1, then the ranks' sums of r^2
+        // all-reduced and the loop test on every rank.  Colours are global and the
+        // Neumann mirrors are written on physical sides only, so p is the
+        // single-domain solve's bit for bit; only the residual's summation order
+        // differs.  The state is read back after every iteration (no batches: the
+        // in-process transport synchronises with the host at every exchange anyway).
+        *g->st_host = s0;
+        if (g->timing) HIPCHK3(hipEventRecord(g->ev[0], g->stream));
+        HIPCHK3(hipMemcpyAsync(g->st, g->st_host, sizeof(DevState), hipMemcpyHostToDevice,
+                               g->stream));
+        int rc;
+        do {
+            for (int pass = 0; pass < 2; ++pass) {
+                if ((rc = exchange_cart(g, MISOR3_P, 7)) != MISOR_OK) return rc;
+                launch3_rb_pass(g->stream, g->g, g->fld[MISOR3_P], g->fld[MISOR3_RHS], pass,
+                                1.0 / dx2, 1.0 / dy2, 1.0 / dz2, factor, g->partials, g->st);
+            }
+            launch3_rb_sum(g->stream, g->g, g->partials, g->st, cells);
+            HIPCHK3(hipGetLastError());
+            if ((rc = allreduce3(g, &g->st->sum[0], 1, false)) != MISOR_OK) return rc;
+            launch3_decide(g->stream, g->st, cells);
+            if (g->timing) HIPCHK3(hipEventRecord(g->ev[1], g->stream));
+            HIPCHK3(hipMemcpyAsync(g->st_host, g->st, sizeof(DevState), hipMemcpyDeviceToHost,
+                                   g->stream));
+            HIPCHK3(hipStreamSynchronize(g->stream));
+        } while (!g->st_host->done);
+        // the final halo, for misor3_adapt_uvw and misor3_download (solver.c:288)
+        if ((rc = exchange_cart(g, MISOR3_P, 7)) != MISOR_OK) return rc;
+        g->alt_stale = true;
+        g->last_iters = g->st_host->it;
+        if (g->timing) {
+            float ms = 0.f;
+            HIPCHK3(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+            g->solve_ms += ms;
+            g->solve_iters += g->st_host->it;
+        }
+        if (iters) *iters = g->st_host->it;
+        if (res) *res = g->st_host->res;
         return MISOR_OK;
     }
     // p resident in LDS, one cooperative launch for the whole solve (ns3d_resident.hip)
@@ -789,6 +1171,12 @@ int misor3_set_tuning(misor_grid3* g, int key, int value) {
     switch (key) {
     case MISOR3_TUNE_SWEEP:
         if (value != 0 && value != 1) return fail3(MISOR_EINVAL, "sweep must be 0 or 1");
+        if (g->cart) {
+            if (value == 1)
+                return fail3(MISOR_EINVAL,
+                             "the fused sweep does not run on a Cartesian process grid");
+            return MISOR_OK;
+        }
         if (value == 0 && dist(g))
             return fail3(MISOR_EINVAL, "the two-pass solve is single-rank only");
         g->sweep = value;
@@ -809,6 +1197,12 @@ int misor3_set_tuning(misor_grid3* g, int key, int value) {
         return MISOR_OK;
     case MISOR3_TUNE_RESIDENT:
         if (value < -1 || value > 1) return fail3(MISOR_EINVAL, "resident must be -1, 0 or 1");
+        if (g->cart) {
+            if (value == 1)
+                return fail3(MISOR_EINVAL,
+                             "the resident solve does not run on a Cartesian process grid");
+            return MISOR_OK;
+        }
         g->resident = value;
         return MISOR_OK;
     }

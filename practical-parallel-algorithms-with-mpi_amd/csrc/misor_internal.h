@@ -385,6 +385,12 @@ struct G3 {
     long long sx, sxy;  // strides of j and k: (I+2), (I+2)(J+2)
     int Kg = 0, koff = 0;            // global planes; global k of local plane 0
     int lo_phys = 1, hi_phys = 1;    // local planes 1 / K border the physical boundary
+    // Cartesian blocks (misor3_create_cart): I, J are the block's cells too.
+    // The defaults are those of a slab / single domain, which spans x and y.
+    int ioff = 0, joff = 0;          // global i, j of local cell 0
+    int Ig = 0, Jg = 0;              // global cells along x, y (0: I, J)
+    int xlo_phys = 1, xhi_phys = 1;  // local columns 1 / I border the physical boundary
+    int ylo_phys = 1, yhi_phys = 1;  // local rows 1 / J
     __host__ __device__ long long ix(int i, int j, int k) const {
         return (long long)k * sxy + (long long)j * sx + i;
     }
@@ -400,6 +406,27 @@ void launch3_rhs(hipStream_t s, const G3& g, const double* f, const double* gg, 
 int launch3_rb_iteration(hipStream_t s, const G3& g, double* p, const double* rhs, double idx2,
                          double idy2, double idz2, double factor, double* partials, DevState* st,
                          double cells);
+// Cartesian blocks: the same iteration in pieces, because an exchange of p
+// goes before each colour pass -- pass 0 / 1 with its partials in
+// partials[pass * nb ..] (returns nb), then the block's sum of r^2 of both
+// passes into st->sum[0] (all-reduce, launch3_decide)
+int launch3_rb_pass(hipStream_t s, const G3& g, double* p, const double* rhs, int pass,
+                    double idx2, double idy2, double idz2, double factor, double* partials,
+                    const DevState* st);
+void launch3_rb_sum(hipStream_t s, const G3& g, const double* partials, DevState* st,
+                    double cells);
+// a box of cells of a field in the reference layout (halo3.hip): nx x ny x nz
+// cells from (x0, y0, z0), strides sx / sxy; packed x fastest
+struct Box3 {
+    int x0, y0, z0, nx, ny, nz;
+    long long sx, sxy;
+    long long cells() const { return (long long)nx * ny * nz; }
+};
+void launch3_box_pack(hipStream_t s, const double* field, const Box3& b, double* buf);
+void launch3_box_unpack(hipStream_t s, double* field, const Box3& b, const double* buf);
+// launch3_absmax over a box instead of a run of cells
+void launch3_absmax_box(hipStream_t s, const double* u, const double* v, const double* w,
+                        const Box3& b, double* partials, double* out);
 // one solve iteration as ONE sweep launch (red then black, src -> dst) plus
 // the loop test; rows in {4, 8, 12}, kc planes per workgroup
 int sweep3_blocks(const G3& g, int rows, int kc);

@@ -92,7 +92,9 @@ __global__ __launch_bounds__(256) void k3_rb_pass(G3 g, double* __restrict__ p,
     if (st->done) return;
     const int j = 1 + blockIdx.y * kBy + threadIdx.y;
     const int k = 1 + blockIdx.z;
-    const int i = 2 * (blockIdx.x * kBx + threadIdx.x) + (((1 + j + k + pass) & 1) ? 1 : 2);
+    // colours are global: pass 0 takes the cells with odd (ioff+i) + (joff+j) + (koff+k)
+    const int i = 2 * (blockIdx.x * kBx + threadIdx.x) +
+                  (((1 + j + k + pass + g.ioff + g.joff + g.koff) & 1) ? 1 : 2);
     double acc = 0.0;
     if (i <= g.I && j <= g.J) {
         const long long q = g.ix(i, j, k);
@@ -104,12 +106,14 @@ __global__ __launch_bounds__(256) void k3_rb_pass(G3 g, double* __restrict__ p,
         const double np = c - (factor * r);
         p[q] = np;
         acc = r * r;
-        if (i == 1) p[q - 1] = np;
-        if (i == g.I) p[q + 1] = np;
-        if (j == 1) p[q - g.sx] = np;
-        if (j == g.J) p[q + g.sx] = np;
-        if (k == 1) p[q - g.sxy] = np;
-        if (k == g.K) p[q + g.sxy] = np;
+        // on a physical side only: next to another rank that cell is the
+        // neighbour's value, filled by the halo exchange
+        if (i == 1 && g.xlo_phys) p[q - 1] = np;
+        if (i == g.I && g.xhi_phys) p[q + 1] = np;
+        if (j == 1 && g.ylo_phys) p[q - g.sx] = np;
+        if (j == g.J && g.yhi_phys) p[q + g.sx] = np;
+        if (k == 1 && g.lo_phys) p[q - g.sxy] = np;
+        if (k == g.K && g.hi_phys) p[q + g.sxy] = np;
     }
     const double s = block_sum256(acc, sh);
     if (threadIdx.x == 0 && threadIdx.y == 0)
@@ -143,7 +147,8 @@ __global__ __launch_bounds__(1024) void k3_finish(const double* __restrict__ par
         }
         __syncthreads();
     }
-    if (t == 0 && sum_only) st->sum[0] = tot[0];  // decomposed: all-reduce, then decide
+    // decomposed: all-reduce, then decide
+    if (t == 0 && sum_only) st->sum[0] = npass > 1 ? tot[0] + tot[1] : tot[0];
     if (t == 0 && !sum_only) {
         double res = st->res + tot[0];
         if (npass > 1) res = res + tot[1];
@@ -618,12 +623,12 @@ __global__ void k3_fg_boundary(G3 g, const double* __restrict__ u, const double*
     const int b = 1 + blockIdx.y;
     if (blockIdx.z == 0) {
         if (a > g.J || b > g.K) return;
-        f[g.ix(0, a, b)] = u[g.ix(0, a, b)];
-        f[g.ix(g.I, a, b)] = u[g.ix(g.I, a, b)];
+        if (g.xlo_phys) f[g.ix(0, a, b)] = u[g.ix(0, a, b)];
+        if (g.xhi_phys) f[g.ix(g.I, a, b)] = u[g.ix(g.I, a, b)];
     } else if (blockIdx.z == 1) {
         if (a > g.I || b > g.K) return;
-        gg[g.ix(a, 0, b)] = v[g.ix(a, 0, b)];
-        gg[g.ix(a, g.J, b)] = v[g.ix(a, g.J, b)];
+        if (g.ylo_phys) gg[g.ix(a, 0, b)] = v[g.ix(a, 0, b)];
+        if (g.yhi_phys) gg[g.ix(a, g.J, b)] = v[g.ix(a, g.J, b)];
     } else {
         if (a > g.I || b > g.J) return;
         if (g.lo_phys) h[g.ix(a, b, 0)] = w[g.ix(a, b, 0)];
@@ -680,11 +685,32 @@ __global__ void k3_wall(G3 g, double* __restrict__ n, double* __restrict__ t1,
 __global__ void k3_special(G3 g, double* __restrict__ u, int problem) {
     const int a = 1 + blockIdx.x * blockDim.x + threadIdx.x;
     const int b = 1 + blockIdx.y;
-    if (problem == MISOR_PROBLEM_DCAVITY) {  // i = 1..imax-1, k = 1..kmax-1
-        if (a < g.I && b <= g.K && g.koff + b < g.Kg)
+    if (problem == MISOR_PROBLEM_DCAVITY) {  // global i = 1..imax-1, k = 1..kmax-1, top ranks
+        const int Ig = g.Ig ? g.Ig : g.I;
+        if (g.yhi_phys && a <= g.I && g.ioff + a < Ig && b <= g.K && g.koff + b < g.Kg)
             u[g.ix(a, g.J + 1, b)] = 2.0 - u[g.ix(a, g.J, b)];
-    } else if (problem == MISOR_PROBLEM_CANAL) {  // U(0,j,k) = 2.0
-        if (a <= g.J && b <= g.K) u[g.ix(0, a, b)] = 2.0;
+    } else if (problem == MISOR_PROBLEM_CANAL) {  // U(0,j,k) = 2.0, left ranks
+        if (g.xlo_phys && a <= g.J && b <= g.K) u[g.ix(0, a, b)] = 2.0;
+    }
+}
+
+// the three maxima of a 256-thread block into partials[3 * block ..]
+__device__ __forceinline__ void absmax3_block(double mu, double mv, double mw, double (*sh)[4],
+                                              double* __restrict__ partials) {
+    mu = wave_max(mu);
+    mv = wave_max(mv);
+    mw = wave_max(mw);
+    const int t = threadIdx.x;
+    if ((t & 63) == 0) {
+        sh[0][t >> 6] = mu;
+        sh[1][t >> 6] = mv;
+        sh[2][t >> 6] = mw;
+    }
+    __syncthreads();
+    if (t < 3) {
+        double m = sh[t][0];
+        for (int x = 1; x < 4; ++x) m = (m > sh[t][x]) ? m : sh[t][x];
+        partials[3 * blockIdx.x + t] = m;
     }
 }
 
@@ -703,21 +729,32 @@ __global__ __launch_bounds__(256) void k3_absmax3(const double* __restrict__ u,
         mv = (mv > b) ? mv : b;
         mw = (mw > c) ? mw : c;
     }
-    mu = wave_max(mu);
-    mv = wave_max(mv);
-    mw = wave_max(mw);
-    const int t = threadIdx.x;
-    if ((t & 63) == 0) {
-        sh[0][t >> 6] = mu;
-        sh[1][t >> 6] = mv;
-        sh[2][t >> 6] = mw;
+    absmax3_block(mu, mv, mw, sh, partials);
+}
+
+// the same over a box of cells: a Cartesian block's owned cells plus the
+// ghost cells on its physical sides -- every cell of the global array belongs
+// to exactly one rank's box, and no inter-rank halo copy enters the maximum
+__global__ __launch_bounds__(256) void k3_absmax3_box(const double* __restrict__ u,
+                                                      const double* __restrict__ v,
+                                                      const double* __restrict__ w, Box3 bx,
+                                                      double* __restrict__ partials) {
+    __shared__ double sh[3][4];
+    double mu = DBL_MIN, mv = DBL_MIN, mw = DBL_MIN;
+    const long long n = (long long)bx.nx * bx.ny * bx.nz;
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) {
+        const int x = (int)(e % bx.nx);
+        const long long r = e / bx.nx;
+        const int y = (int)(r % bx.ny), z = (int)(r / bx.ny);
+        const long long q = (long long)(bx.z0 + z) * bx.sxy + (long long)(bx.y0 + y) * bx.sx +
+                            (bx.x0 + x);
+        const double a = fabs(u[q]), b = fabs(v[q]), c = fabs(w[q]);
+        mu = (mu > a) ? mu : a;
+        mv = (mv > b) ? mv : b;
+        mw = (mw > c) ? mw : c;
     }
-    __syncthreads();
-    if (t < 3) {
-        double m = sh[t][0];
-        for (int x = 1; x < 4; ++x) m = (m > sh[t][x]) ? m : sh[t][x];
-        partials[3 * blockIdx.x + t] = m;
-    }
+    absmax3_block(mu, mv, mw, sh, partials);
 }
 
 __global__ __launch_bounds__(256) void k3_max_finish(const double* __restrict__ partials, int nb,
@@ -812,6 +849,23 @@ int launch3_rb_iteration(hipStream_t s, const G3& g, double* p, const double* rh
     return nb;
 }
 
+int launch3_rb_pass(hipStream_t s, const G3& g, double* p, const double* rhs, int pass,
+                    double idx2, double idy2, double idz2, double factor, double* partials,
+                    const DevState* st) {
+    const dim3 grid = cells_grid(g, (g.I + 1) / 2);
+    const int nb = (int)(grid.x * grid.y * grid.z);
+    hipLaunchKernelGGL(k3_rb_pass, grid, dim3(kBx, kBy), 0, s, g, p, rhs, pass, idx2, idy2, idz2,
+                       factor, partials + (long long)pass * nb, st);
+    return nb;
+}
+
+void launch3_rb_sum(hipStream_t s, const G3& g, const double* partials, DevState* st,
+                    double cells) {
+    const dim3 grid = cells_grid(g, (g.I + 1) / 2);
+    hipLaunchKernelGGL(k3_finish, dim3(1), dim3(1024), 0, s, partials,
+                       (int)(grid.x * grid.y * grid.z), 2, st, cells, 1);
+}
+
 int sweep3_blocks(const G3& g, int rows, int kc) {
     const long long nstr = (g.I + kSwOwn - 1) / kSwOwn, nrb = (g.J + rows - 1) / rows,
                     nkc = (g.K + kc - 1) / kc;
@@ -903,6 +957,13 @@ int absmax3_blocks() { return 1024; }
 void launch3_absmax(hipStream_t s, const double* u, const double* v, const double* w,
                     long long n, double* partials, double* out) {
     hipLaunchKernelGGL(k3_absmax3, dim3(absmax3_blocks()), dim3(256), 0, s, u, v, w, n,
+                       partials);
+    hipLaunchKernelGGL(k3_max_finish, dim3(1), dim3(256), 0, s, partials, absmax3_blocks(), out);
+}
+
+void launch3_absmax_box(hipStream_t s, const double* u, const double* v, const double* w,
+                        const Box3& b, double* partials, double* out) {
+    hipLaunchKernelGGL(k3_absmax3_box, dim3(absmax3_blocks()), dim3(256), 0, s, u, v, w, b,
                        partials);
     hipLaunchKernelGGL(k3_max_finish, dim3(1), dim3(256), 0, s, partials, absmax3_blocks(), out);
 }

@@ -8,6 +8,9 @@
  * "nt t dt iterations".  MISOR_RANKS=N (or a launcher's WORLD_SIZE/RANK,
  * host/ranks.h) runs it decomposed into N slabs of planes like the
  * reference's mpirun -np N; rank 0 prints and writes the collected result.
+ * MISOR_DIMS=XxYxZ splits the box over that 3D Cartesian process grid instead
+ * of slabs, as the reference's MPI_Dims_create / MPI_Cart_create does (a 0
+ * entry is chosen automatically: MISOR_DIMS=0x0x0 with 8 ranks is 2x2x2).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -100,6 +103,8 @@ int main(int argc, char** argv)
         exit(EXIT_SUCCESS);
     }
     readParameter(&p, argv[1]);
+    int dims[3];
+    (void)rankDims(dims); /* a malformed MISOR_DIMS ends the program here, before any rank starts */
     const char* r = getenv("RANK");
     if (!r || atoi(r) == 0) printParameter3D(&p);
     fflush(stdout);

@@ -37,6 +37,19 @@ static int env_int(const char* name, int dflt)
     return (s && *s) ? atoi(s) : dflt;
 }
 
+int rankDims(int dims[3])
+{
+    const char* s = getenv("MISOR_DIMS");
+    if (!s || !*s) return 0;
+    char tail = 0;
+    if (sscanf(s, "%dx%dx%d%c", &dims[0], &dims[1], &dims[2], &tail) != 3 || dims[0] < 0 ||
+        dims[1] < 0 || dims[2] < 0) {
+        printf("Error: MISOR_DIMS=%s is not XxYxZ\n", s);
+        exit(EXIT_FAILURE);
+    }
+    return 1;
+}
+
 /* the communicator id of this launch: rank 0 creates and publishes it, the
  * others read it (comm_file.h); rank 0 removes the file when the program ends */
 static char comm_path[1024];

@@ -12,6 +12,10 @@
  *     publishes the communicator id in a file tagged with the launch
  *     (comm_file.h: MISOR_COMM_FILE, default /tmp/misor_comm_<WORLD_SIZE>_<tag>.id).
  * With neither set the program is the single-GPU one.
+ *
+ * The 3D program splits its box into slabs of planes; MISOR_DIMS=XxYxZ selects
+ * the reference's 3D Cartesian process grid instead (a 0 entry: automatic, so
+ * 0x0x0 is MPI_Dims_create's choice for the rank count).
  */
 #ifndef MISOR_HOST_RANKS_H
 #define MISOR_HOST_RANKS_H
@@ -27,4 +31,7 @@ typedef struct {
 int runRanks(int (*fn)(const RankCtx*, void*), void* arg);
 /* the calling thread's rank (valid inside fn; rank 0 of 1 otherwise) */
 const RankCtx* currentRank(void);
+/* MISOR_DIMS=XxYxZ into dims {x, y, z}: 1 if it is set, 0 if not (slabs); a
+ * value that is not three non-negative integers ends the program */
+int rankDims(int dims[3]);
 #endif

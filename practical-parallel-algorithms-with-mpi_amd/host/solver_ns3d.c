@@ -77,7 +77,8 @@ void initSolver(Solver* s, Parameter* params)
     d.bcFront = s->bcFront;
     d.bcBack = s->bcBack;
     d.problem = problemId(s->problem);
-    /* decomposed runs (host/ranks.h): slabs of planes, one rank per GPU */
+    /* decomposed runs (host/ranks.h): slabs of planes, one rank per GPU; with
+     * MISOR_DIMS the reference's 3D Cartesian process grid */
     const RankCtx* rk = currentRank();
     d.device = rk->size > 1 ? rk->device : -1;
     d.nranks = rk->size;
@@ -85,7 +86,11 @@ void initSolver(Solver* s, Parameter* params)
     d.comm_id = rk->comm_id;
     s->rank = rk->rank;
     s->size = rk->size;
-    misorCheck(misor3_create(&s->dev, &d), "initSolver");
+    int dims[3];
+    if (rk->size > 1 && rankDims(dims))
+        misorCheck(misor3_create_cart(&s->dev, &d, dims), "initSolver");
+    else
+        misorCheck(misor3_create(&s->dev, &d), "initSolver");
     misorCheck(misor3_fill(s->dev, MISOR3_U, params->u_init), "initSolver");
     misorCheck(misor3_fill(s->dev, MISOR3_V, params->v_init), "initSolver");
     misorCheck(misor3_fill(s->dev, MISOR3_W, params->w_init), "initSolver");

@@ -81,6 +81,11 @@ class Desc3(C.Structure):
                 ("rank", C.c_int), ("comm_id", C.c_void_p)]
 
 
+class Local3(C.Structure):
+    _fields_ = [("n", C.c_int * 3), ("off", C.c_int * 3), ("coords", C.c_int * 3),
+                ("dims", C.c_int * 3), ("neighbours", C.c_int * 6)]
+
+
 # every exported symbol of include/misor.h, with its ctypes signature
 SIGNATURES = {
     "misor_last_error": (C.c_char_p, []),
@@ -145,6 +150,12 @@ SIGNATURES = {
     "misor3_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "misor3_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "misor3_get_solve_time": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_longlong)]),
+    "misor3_decompose_cart": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int,
+                                        C.c_int, C.POINTER(Local3)]),
+    "misor3_create_cart": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(Desc3),
+                                     C.POINTER(C.c_int)]),
+    "misor3_local_info_cart": (C.c_int, [C.c_void_p, C.POINTER(Local3)]),
+    "misor3_exchange": (C.c_int, [C.c_void_p, C.c_int]),
 }
 
 _lib = None
@@ -376,12 +387,24 @@ def decompose3(nranks, rank, kmax):
     return a.value, b.value
 
 
+def decompose3_cart(nranks, rank, imax, jmax, kmax, dims=(0, 0, 0)):
+    """the Local3 block of `rank` on the process grid dims = (x, y, z); 0: automatic"""
+    loc = Local3()
+    d = (C.c_int * 3)(*dims)
+    _check(lib().misor3_decompose_cart(nranks, rank, d, imax, jmax, kmax, C.byref(loc)))
+    return loc
+
+
 class Grid3:
     """The 3D solver (assignment-6/src/solver.c): fields of shape
     (kloc+2, jmax+2, imax+2), A(i,j,k) = a[k, j, i] (solver.c:19-34); kloc =
-    kmax on one GPU, the rank's slab when decomposed (nranks > 1)."""
+    kmax on one GPU, the rank's slab when decomposed (nranks > 1).  With dims =
+    (x, y, z) the box is split over that Cartesian process grid instead (0
+    entries: automatic): fields of shape (nk+2, nj+2, ni+2) with .n = (ni, nj,
+    nk), and .off, .coords, .dims, .neighbours as misor3_local."""
 
-    def __init__(self, prm: dict, device=-1, nranks=1, rank=0, comm_id: bytes | None = None):
+    def __init__(self, prm: dict, device=-1, nranks=1, rank=0, comm_id: bytes | None = None,
+                 dims=None):
         d = Desc3()
         d.imax, d.jmax, d.kmax = int(prm["imax"]), int(prm["jmax"]), int(prm["kmax"])
         d.xlength, d.ylength, d.zlength = prm["xlength"], prm["ylength"], prm["zlength"]
@@ -396,13 +419,21 @@ class Grid3:
         self._id = C.create_string_buffer(comm_id, COMM_ID_BYTES) if comm_id else None
         d.comm_id = C.cast(self._id, C.c_void_p) if self._id is not None else None
         self.h = C.c_void_p()
-        _check(lib().misor3_create(C.byref(self.h), C.byref(d)))
+        if dims is None:
+            _check(lib().misor3_create(C.byref(self.h), C.byref(d)))
+        else:
+            _check(lib().misor3_create_cart(C.byref(self.h), C.byref(d), (C.c_int * 3)(*dims)))
         self.desc = d
         a, b = C.c_int(0), C.c_int(0)
         _check(lib().misor3_local_info(self.h, C.byref(a), C.byref(b)))
         self.kloc, self.koff = a.value, b.value
         self.rank, self.nranks = rank, nranks
-        self.shape = (self.kloc + 2, d.jmax + 2, d.imax + 2)
+        loc = Local3()
+        _check(lib().misor3_local_info_cart(self.h, C.byref(loc)))
+        self.n, self.off = tuple(loc.n), tuple(loc.off)
+        self.coords, self.dims = tuple(loc.coords), tuple(loc.dims)
+        self.neighbours = tuple(loc.neighbours)
+        self.shape = (self.n[2] + 2, self.n[1] + 2, self.n[0] + 2)
         self.global_shape = (d.kmax + 2, d.jmax + 2, d.imax + 2)
 
     def close(self):
@@ -443,6 +474,11 @@ class Grid3:
             return out
         _check(lib().misor3_gather(self.h, field, C.cast(None, _dp)))
         return None
+
+    def exchange(self, field):
+        """the 1-deep halo of `field`, edges and corners included (collective;
+        Cartesian grids)"""
+        _check(lib().misor3_exchange(self.h, field))
 
     def set_dt(self, dt):
         _check(lib().misor3_set_dt(self.h, dt))
