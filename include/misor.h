@@ -329,6 +329,62 @@ int misor_enable_timing(misor_grid* g, int on);
 int misor_get_stats(const misor_grid* g, misor_stats* out);
 int misor_reset_stats(misor_grid* g);
 
+/* --------------------------------------------------------------- batch ---
+ * Many small Poisson problems of ONE shape solved in one launch: nbatch
+ * independent members, each with its own p, rhs, omega, eps and itermax, one
+ * workgroup per member with its p resident in LDS (the whole-solve kernel of
+ * MISOR_TUNE_SMALL_SOLVE; the relaxation-factor study around poisson.par's
+ * omg, a sweep over eps, many right-hand sides on one mesh).  Single rank.
+ *
+ * Contract
+ *  - For every member m, p, iters[m] and res[m] are the same bits as
+ *    misor_solve_rb gives on a single-rank misor_grid of that shape with
+ *    member m's omega, eps, itermax, p and rhs, at the same
+ *    MISOR_TUNE_NEAR_BAND.  (A member whose residual comes within the near
+ *    band of eps^2 is finished through that very path on an internal grid.)
+ *  - Members are independent: one member's convergence, cap or data never
+ *    affects another.
+ *  - The batch holds LDS-resident problems only: a shape the whole-solve
+ *    kernel does not hold (more than 128^2 cells) is MISOR_EINVAL; use
+ *    misor_create for those.  imax or jmax of 1 is accepted; misor_create
+ *    has no such grid, so there the batch's own fixed-order residual sum
+ *    decides the loop test and MISOR_TUNE_NEAR_BAND has no effect.
+ *  - Argument errors (below) are found before any device call.  The device
+ *    is first touched, and its memory allocated, by the first call that moves
+ *    or computes data, which may so return MISOR_EHIP / MISOR_ENOMEM. */
+typedef struct misor_batch misor_batch;
+
+typedef struct {
+    int imax, jmax;      /* one shape for the whole batch */
+    double dx, dy;
+    int nbatch;          /* >= 1 */
+    int variant;         /* MISOR_SOLVE_RB / MISOR_SOLVE_RBA, whole batch */
+    int device;          /* -1: current */
+} misor_batch_desc;
+
+/* MISOR_EINVAL: a null pointer, imax or jmax < 1, dx or dy <= 0, nbatch < 1,
+ * an unknown variant, a shape that does not fit in LDS */
+int misor_batch_create(misor_batch** out, const misor_batch_desc* d);
+void misor_batch_destroy(misor_batch* b);
+/* per-member SOR parameters, arrays of nbatch; a NULL array keeps what is set.
+ * Defaults after create: omega 1.0, eps 0.0, itermax 0 */
+int misor_batch_set_params(misor_batch* b, const double* omega, const double* eps,
+                           const int* itermax);
+/* field = MISOR_P or MISOR_RHS; member in [0, nbatch) moves one (imax+2)(jmax+2)
+ * array in the reference layout; member = -1 moves nbatch of them, contiguous.
+ * MISOR_EINVAL: null pointer, another field, a member out of range */
+int misor_batch_upload(misor_batch* b, int field, int member, const double* host);
+int misor_batch_download(misor_batch* b, int field, int member, double* host);
+/* assignment-4 initSolver fields into every member (as misor_poisson_init) */
+int misor_batch_poisson_init(misor_batch* b, double xlength, double ylength, int problem);
+/* solveRB / solveRBA on every member; iters / res: arrays of nbatch, either may be NULL */
+int misor_batch_solve_rb(misor_batch* b, int* iters, double* res);
+/* stream the batch's kernel runs on (hipStream_t as void*); NULL = own stream */
+int misor_batch_set_stream(misor_batch* b, void* hip_stream);
+/* MISOR_TUNE_NEAR_BAND only (as on a grid); any other key is MISOR_EINVAL */
+int misor_batch_set_tuning(misor_batch* b, int key, int value);
+int misor_batch_get_tuning(const misor_batch* b, int key, int* value);
+
 /* ------------------------------------------------------------------ 3D ---
  * assignment-6's 3D Navier-Stokes solver (assignment-6/src/solver.c) on one
  * GPU: the same step as solver.h's computeTimestep / setBoundaryConditions /

@@ -91,6 +91,22 @@ int misor_comm_unique_id(void* id_out) {
     return MISOR_OK;
 }
 
+SorConsts sor_consts(double dx, double dy, double omega, int variant) {
+    const double dx2 = dx * dx, dy2 = dy * dy;
+    SorConsts c{};
+    c.idx2 = 1.0 / dx2;
+    c.idy2 = 1.0 / dy2;
+    if (variant == MISOR_SOLVE_RBA) {
+        const double factor = 0.5 * (dx2 * dy2) / (dx2 + dy2);  // solver.c:250
+        c.coef = omega * factor;                                // (omega*factor)*r, :273
+    } else {
+        c.coef = omega * 0.5 * (dx2 * dy2) / (dx2 + dy2);  // solver.c:189
+    }
+    return c;
+}
+
+double near_band_rel(int value) { return value >= 300 ? 0.0 : pow(10.0, -(double)value); }
+
 void misor_destroy(misor_grid* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
@@ -238,20 +254,15 @@ int misor_create(misor_grid** out, const misor_desc* d) {
     sp.red_hi_i = sp.ghost_right ? L.ni : L.ni + 1;
     sp.red_lo_j = sp.ghost_bottom ? 1 : 0;
     sp.red_hi_j = sp.ghost_top ? L.nj : L.nj + 1;
-    const double dx2 = d->dx * d->dx, dy2 = d->dy * d->dy;
-    sp.idx2 = 1.0 / dx2;
-    sp.idy2 = 1.0 / dy2;
+    const SorConsts sc = sor_consts(d->dx, d->dy, d->omega, d->variant);
+    sp.idx2 = sc.idx2;
+    sp.idy2 = sc.idy2;
+    sp.coef = sc.coef;
     {
         // power-of-two spacing (sor_tb.h resid<true>): 1/dx^2 == 1/dy^2 == 2^m, m >= 0
         int e = 0;
         const double mant = frexp(sp.idx2, &e);
         sp.pow2 = sp.idx2 == sp.idy2 && mant == 0.5 && e >= 1;
-    }
-    if (d->variant == MISOR_SOLVE_RBA) {
-        const double factor = 0.5 * (dx2 * dy2) / (dx2 + dy2);  // solver.c:250
-        sp.coef = d->omega * factor;                            // (omega*factor)*r, :273
-    } else {
-        sp.coef = d->omega * 0.5 * (dx2 * dy2) / (dx2 + dy2);  // solver.c:189
     }
     if (configure_sweep(g, kDefaultSweepVariant, 0, 1) != MISOR_OK) {
         misor_destroy(g);
@@ -441,8 +452,29 @@ int misor_upload(misor_grid* g, int field, const double* host) {
     return MISOR_OK;
 }
 
+// A single-rank grid takes over one problem of its own shape that already lies
+// on the device in the padded layout (a member of a misor_batch): what
+// misor_create derives from omega, eps and itermax, then p and rhs as
+// misor_upload leaves them.  Enqueued on the grid's stream.
+int grid_adopt(misor_grid* g, const double* p_dev, const double* rhs_dev, double omega, double eps,
+               int itermax) {
+    g->desc.omega = omega;
+    g->desc.eps = eps;
+    g->desc.itermax = itermax;
+    g->sp.coef = g->tp.coef = sor_consts(g->desc.dx, g->desc.dy, omega, g->desc.variant).coef;
+    const size_t bytes = (size_t)g->elems * sizeof(double);
+    g->cur = 0;
+    g->p_stale = false;
+    g->rhs_halo = 0;
+    ++g->fgr_ver;
+    for (int b = 0; b < g->np; ++b)
+        HIPCHK(hipMemcpyAsync(pbuf(g, b), p_dev, bytes, hipMemcpyDeviceToDevice, g->stream));
+    HIPCHK(hipMemcpyAsync(g->fld[kRhs], rhs_dev, bytes, hipMemcpyDeviceToDevice, g->stream));
+    return MISOR_OK;
+}
+
 #ifdef MISOR_PROXY
-#define PROXYCHK(g)                                                                        \
+#define PROXYCHK(g)                                                                       \
     do {                                                                                   \
         if ((g)->proxy)                                                                    \
             return fail(MISOR_ESTATE, "a MISOR_PROXY_SIDES grid holds no meaningful field"); \
@@ -641,29 +673,33 @@ int misor_fill(misor_grid* g, int field, double value) {
     return MISOR_OK;
 }
 
+std::vector<double> poisson_tables(const misor_local& loc, int imax, int jmax, double xlength,
+                                   double ylength) {
+    const int ni = loc.ni, nj = loc.nj;
+    const double PI = 3.14159265358979323846;  // assignment-4/src/solver.c:15
+    const double dx = xlength / imax, dy = ylength / jmax;
+    // host tables with the reference's exact expressions (solver.c:107,114)
+    std::vector<double> tab((size_t)(2 * (ni + 2) + (nj + 2)));
+    double *sx = tab.data(), *rx = sx + (ni + 2), *sy = rx + (ni + 2);
+    for (int i = 0; i < ni + 2; ++i) {
+        const int gi = loc.ioff + i;
+        sx[i] = sin(2.0 * PI * gi * dx * 2.0);
+        rx[i] = sin(2.0 * PI * gi * dx);
+    }
+    for (int j = 0; j < nj + 2; ++j) sy[j] = sin(2.0 * PI * (loc.joff + j) * dy * 2.0);
+    return tab;
+}
+
 int misor_poisson_init(misor_grid* g, double xlength, double ylength, int problem) {
     if (!g) return fail(MISOR_EINVAL, "null grid");
     HIPCHK(hipSetDevice(g->device));
     const int ni = g->loc.ni, nj = g->loc.nj;
-    const double PI = 3.14159265358979323846;  // assignment-4/src/solver.c:15
-    const double dx = xlength / g->desc.imax, dy = ylength / g->desc.jmax;
-    // host tables with the reference's exact expressions (solver.c:107,114)
-    std::vector<double> sx(ni + 2), sy(nj + 2), rx(ni + 2);
-    for (int i = 0; i < ni + 2; ++i) {
-        const int gi = g->loc.ioff + i;
-        sx[i] = sin(2.0 * PI * gi * dx * 2.0);
-        rx[i] = sin(2.0 * PI * gi * dx);
-    }
-    for (int j = 0; j < nj + 2; ++j) sy[j] = sin(2.0 * PI * (g->loc.joff + j) * dy * 2.0);
+    const std::vector<double> host =
+        poisson_tables(g->loc, g->desc.imax, g->desc.jmax, xlength, ylength);
     double* tab = nullptr;
-    const size_t n = (size_t)(2 * (ni + 2) + (nj + 2));
-    HIPCHK(hipMalloc(&tab, n * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(tab, sx.data(), (ni + 2) * sizeof(double), hipMemcpyHostToDevice,
+    HIPCHK(hipMalloc(&tab, host.size() * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice,
                           g->stream));
-    HIPCHK(hipMemcpyAsync(tab + (ni + 2), rx.data(), (ni + 2) * sizeof(double),
-                          hipMemcpyHostToDevice, g->stream));
-    HIPCHK(hipMemcpyAsync(tab + 2 * (ni + 2), sy.data(), (nj + 2) * sizeof(double),
-                          hipMemcpyHostToDevice, g->stream));
     g->cur = 0;
     g->p_stale = false;
     g->rhs_halo = 0;
@@ -742,7 +778,7 @@ int misor_set_tuning(misor_grid* g, int key, int value) {
         return MISOR_OK;
     case MISOR_TUNE_NEAR_BAND:
         g->near_exp = value;
-        g->near_rel = value >= 300 ? 0.0 : pow(10.0, -(double)value);
+        g->near_rel = near_band_rel(value);
         return MISOR_OK;
     case MISOR_TUNE_RES_LITE:
         if (value != 0 && value != 1) return fail(MISOR_EINVAL, "RES_LITE is 0 or 1");

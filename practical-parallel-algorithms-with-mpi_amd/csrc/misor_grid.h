@@ -244,6 +244,29 @@ inline double* pbuf(misor_grid* g, long long x) {
 
 // ---- shared helpers (defined in the unit named beside each group) ----
 
+// misor_api.hip
+// the scalars solveRB / solveRBA derive from the spacing and omega
+// (assignment-4/src/solver.c:185-189, 250): 1/dx^2, 1/dy^2 and the update's
+// factor (RB: omega inside; RBA: omega * factor)
+struct SorConsts {
+    double idx2, idy2, coef;
+};
+MISOR_HIDDEN SorConsts sor_consts(double dx, double dy, double omega, int variant);
+// assignment-4 initSolver's 1-D sine tables of a block, packed for
+// launch_poisson_init: sx (ni + 2), rx (ni + 2), sy (nj + 2)
+MISOR_HIDDEN std::vector<double> poisson_tables(const misor_local& loc, int imax, int jmax,
+                                                double xlength, double ylength);
+// MISOR_TUNE_NEAR_BAND's value as the relative band of eps^2 (0: off)
+MISOR_HIDDEN double near_band_rel(int value);
+// the loop state's band (DevState::nband) of a solve to eps^2 = epssq; < 0: none
+// (eps^2 = 0 -- e.g. eps = 1e-300 -- has no threshold to come near: res >= 0
+// always continues the loop)
+inline double near_band_abs(double near_rel, double epssq) {
+    return near_rel > 0.0 && epssq > 0.0 ? near_rel * epssq : -1.0;
+}
+MISOR_HIDDEN int grid_adopt(misor_grid* g, const double* p_dev, const double* rhs_dev,
+                            double omega, double eps, int itermax);
+
 // misor_comm.hip
 MISOR_HIDDEN int allreduce(misor_grid* g, double* dev, int n, int is_max, hipStream_t s = nullptr);
 MISOR_HIDDEN void build_plan(misor_grid* g, int d);

@@ -306,6 +306,15 @@ int small_solve_fits(int ni, int nj);
 void launch_solve_small(hipStream_t s, double* p, const double* rhs, int ni, int nj,
                         long long pitch, double idx2, double idy2, double coef, double cells,
                         DevState* st);
+// the same solve for a batch of problems of one shape, one workgroup each
+// (sor_kernels.hip rb_solve_batch_kernel): what differs between the members
+struct BatchMember {
+    double coef;  // omega is per member
+    DevState st;  // loop state in, it / res / near out
+};
+void launch_solve_batch(hipStream_t s, double* p_base, const double* rhs_base,
+                        long long member_stride, int nbatch, int ni, int nj, long long pitch,
+                        double idx2, double idy2, double cells, BatchMember* members);
 
 // 8-neighbour halo exchange of one field (halo.hip): regions in local cell
 // coordinates; direction order L, R, B, T, BL, BR, TL, TR

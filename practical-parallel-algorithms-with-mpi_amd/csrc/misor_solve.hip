@@ -205,6 +205,10 @@ static int solve_small(misor_grid* g, int it0, double res0, double cells, int* i
         launch_solve_small(g->stream, p, g->fld[kRhs], g->loc.ni, g->loc.nj, g->pitch, g->sp.idx2,
                            g->sp.idy2, g->sp.coef, cells, g->st);
         HIPCHK(hipGetLastError());
+        // the exact tail writes its own loop state into the pinned st_host at
+        // once: this run's copy of it must have left first (a grid's second
+        // near-threshold solve, rsq already allocated, got there before it)
+        MISOR_TRY(wait_stream(g, g->stream));
         *hand_off = true;  // the exact tail from iteration it (misor_solve_rb_n)
         return MISOR_OK;
     }
@@ -616,10 +620,7 @@ int solve_rb_from(misor_grid* g, int itermax, int it0, double res0, int* iters, 
         *res = res0;
         return MISOR_OK;
     }
-    // (eps^2 = 0 -- e.g. eps = 1e-300 -- has no threshold to come near: res >= 0
-    // always continues the loop)
-    MISOR_TRY(upload_state(g, it0, res0, itermax,
-                           g->near_rel > 0.0 && epssq > 0.0 ? g->near_rel * epssq : -1.0));
+    MISOR_TRY(upload_state(g, it0, res0, itermax, near_band_abs(g->near_rel, epssq)));
     const double cells = (double)g->desc.imax * (double)g->desc.jmax;
     if (!g->dist && g->small_solve && small_solve_fits(g->loc.ni, g->loc.nj))
         return solve_small(g, it0, res0, cells, iters, res, hand_off);

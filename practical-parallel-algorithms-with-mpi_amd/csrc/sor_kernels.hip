@@ -622,10 +622,14 @@ int small_solve_fits(int ni, int nj) {
     return cells * 8 + 256 <= 160 * 1024 && pairs <= (long long)kSmallThreads * kSmallMaxPairs;
 }
 
-__global__ __launch_bounds__(kSmallThreads) void rb_solve_small_kernel(
-    double* __restrict__ p_glob, const double* __restrict__ rhs_glob, int ni, int nj,
+// The solve of one problem by one workgroup of kSmallThreads threads: the body
+// of rb_solve_small_kernel (one problem a launch) and of rb_solve_batch_kernel
+// (one problem a workgroup), which so give the same bits for p, it and res.
+// lds: 8 * (32 + (ni+2)(nj+2)) bytes of the workgroup's own; everything else
+// describes the problem and may differ between the workgroups of a launch.
+__device__ __forceinline__ void rb_solve_small_body(
+    double* lds, double* __restrict__ p_glob, const double* __restrict__ rhs_glob, int ni, int nj,
     long long pitch, double idx2, double idy2, double coef, double cells, DevState* st) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
     double* red = lds;          // 16 wave partials + broadcast slot
     double* P = lds + 32;       // (ni+2) x (nj+2), row stride ni+2
     const int W = ni + 2;
@@ -725,10 +729,47 @@ __global__ __launch_bounds__(kSmallThreads) void rb_solve_small_kernel(
     }
 }
 
+__global__ __launch_bounds__(kSmallThreads) void rb_solve_small_kernel(
+    double* __restrict__ p_glob, const double* __restrict__ rhs_glob, int ni, int nj,
+    long long pitch, double idx2, double idy2, double coef, double cells, DevState* st) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    rb_solve_small_body(lds, p_glob, rhs_glob, ni, nj, pitch, idx2, idy2, coef, cells, st);
+}
+
+// A batch of problems of one shape (misor_batch.hip): workgroup m solves member
+// m, whose p and rhs lie member_stride doubles after member m - 1's in the
+// single grid's padded layout, with its own coef (omega) and loop state.  The
+// workgroups share nothing and never wait on each other: the hardware runs as
+// many as fit (one per CU from 100^2 on: ~80-135 KB of LDS) and queues the rest.
+__global__ __launch_bounds__(kSmallThreads) void rb_solve_batch_kernel(
+    double* __restrict__ p_base, const double* __restrict__ rhs_base, long long member_stride,
+    int ni, int nj, long long pitch, double idx2, double idy2, double cells,
+    BatchMember* __restrict__ members) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    BatchMember* mb = members + blockIdx.x;
+    const long long off = (long long)blockIdx.x * member_stride;
+    rb_solve_small_body(lds, p_base + off, rhs_base + off, ni, nj, pitch, idx2, idy2, mb->coef,
+                        cells, &mb->st);
+}
+
+static size_t small_solve_lds(int ni, int nj) {
+    return sizeof(double) * (32 + (size_t)(ni + 2) * (nj + 2));
+}
+
+void launch_solve_batch(hipStream_t s, double* p_base, const double* rhs_base,
+                        long long member_stride, int nbatch, int ni, int nj, long long pitch,
+                        double idx2, double idy2, double cells, BatchMember* members) {
+    const size_t lds = small_solve_lds(ni, nj);
+    (void)hipFuncSetAttribute((const void*)rb_solve_batch_kernel,
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(rb_solve_batch_kernel, dim3((unsigned)nbatch), dim3(kSmallThreads), lds, s,
+                       p_base, rhs_base, member_stride, ni, nj, pitch, idx2, idy2, cells, members);
+}
+
 void launch_solve_small(hipStream_t s, double* p, const double* rhs, int ni, int nj,
                         long long pitch, double idx2, double idy2, double coef, double cells,
                         DevState* st) {
-    const size_t lds = sizeof(double) * (32 + (size_t)(ni + 2) * (nj + 2));
+    const size_t lds = small_solve_lds(ni, nj);
     (void)hipFuncSetAttribute((const void*)rb_solve_small_kernel,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(rb_solve_small_kernel, dim3(1), dim3(kSmallThreads), lds, s, p, rhs, ni,

@@ -52,6 +52,11 @@ class NsDesc(C.Structure):
                 ("bcBottom", C.c_int), ("bcTop", C.c_int), ("problem", C.c_int)]
 
 
+class BatchDesc(C.Structure):
+    _fields_ = [("imax", C.c_int), ("jmax", C.c_int), ("dx", C.c_double), ("dy", C.c_double),
+                ("nbatch", C.c_int), ("variant", C.c_int), ("device", C.c_int)]
+
+
 class Local(C.Structure):
     _fields_ = [("ni", C.c_int), ("nj", C.c_int), ("ioff", C.c_int), ("joff", C.c_int),
                 ("coords", C.c_int * 2), ("dims", C.c_int * 2), ("neighbours", C.c_int * 4),
@@ -126,6 +131,16 @@ SIGNATURES = {
     "misor_reset_stats": (C.c_int, [C.c_void_p]),
     "misor_chain_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong,
                                     C.POINTER(C.c_longlong)]),
+    "misor_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(BatchDesc)]),
+    "misor_batch_destroy": (None, [C.c_void_p]),
+    "misor_batch_set_params": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(C.c_int)]),
+    "misor_batch_upload": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
+    "misor_batch_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp]),
+    "misor_batch_poisson_init": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "misor_batch_solve_rb": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _dp]),
+    "misor_batch_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "misor_batch_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "misor_batch_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "misor3_decompose": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                    C.POINTER(C.c_int)]),
     "misor3_create": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(Desc3)]),
@@ -375,6 +390,88 @@ class Grid:
         out = np.zeros(n.value, dtype=np.uint64)
         _check(lib().misor_chain_trace(self.h, out.ctypes.data, n.value, C.byref(n)))
         return out.reshape(-1, 3)
+
+
+class Batch:
+    """nbatch independent Poisson problems of one shape, solved in one launch
+    (misor_batch_*): per-member omega, eps, itermax, p and rhs.  Host arrays
+    are (nbatch, jmax+2, imax+2), or (jmax+2, imax+2) for one member."""
+
+    def __init__(self, imax, jmax, dx, dy, nbatch, variant=SOLVE_RB, device=-1):
+        d = BatchDesc()
+        d.imax, d.jmax, d.dx, d.dy = imax, jmax, dx, dy
+        d.nbatch, d.variant, d.device = nbatch, variant, device
+        self.h = C.c_void_p()
+        _check(lib().misor_batch_create(C.byref(self.h), C.byref(d)))
+        self.desc = d
+        self.imax, self.jmax, self.nbatch = imax, jmax, nbatch
+        self.shape = (jmax + 2, imax + 2)
+
+    def close(self):
+        if self.h:
+            lib().misor_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _per_member(self, v, dtype):
+        """None, a scalar for every member, or a length-nbatch sequence"""
+        if v is None:
+            return None
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (self.nbatch,)))
+        return a
+
+    def set_params(self, omega=None, eps=None, itermax=None):
+        om = self._per_member(omega, np.float64)
+        ep = self._per_member(eps, np.float64)
+        im = self._per_member(itermax, np.intc)
+        _check(lib().misor_batch_set_params(
+            self.h, None if om is None else _ptr(om), None if ep is None else _ptr(ep),
+            None if im is None else im.ctypes.data_as(C.POINTER(C.c_int))))
+
+    def upload(self, field, arr, member=None):
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        want = self.shape if member is not None else (self.nbatch,) + self.shape
+        assert a.shape == want, (a.shape, want)
+        _check(lib().misor_batch_upload(self.h, field, -1 if member is None else member, _ptr(a)))
+
+    def download(self, field, member=None):
+        a = np.empty(self.shape if member is not None else (self.nbatch,) + self.shape)
+        _check(lib().misor_batch_download(self.h, field, -1 if member is None else member,
+                                          _ptr(a)))
+        return a
+
+    def poisson_init(self, xlength, ylength, problem=2):
+        _check(lib().misor_batch_poisson_init(self.h, xlength, ylength, problem))
+
+    def solve_rb(self):
+        """(iters, res): int and float64 arrays of nbatch"""
+        it = np.zeros(self.nbatch, dtype=np.intc)
+        res = np.zeros(self.nbatch)
+        _check(lib().misor_batch_solve_rb(self.h, it.ctypes.data_as(C.POINTER(C.c_int)),
+                                          _ptr(res)))
+        return it, res
+
+    def set_stream(self, stream_ptr):
+        _check(lib().misor_batch_set_stream(self.h, C.c_void_p(stream_ptr)))
+
+    def set_tuning(self, key, value):
+        _check(lib().misor_batch_set_tuning(self.h, key, value))
+
+    def get_tuning(self, key):
+        v = C.c_int(0)
+        _check(lib().misor_batch_get_tuning(self.h, key, C.byref(v)))
+        return v.value
 
 
 _PROBLEMS = {"dcavity": PROBLEM_DCAVITY, "canal": PROBLEM_CANAL}
