@@ -129,6 +129,14 @@ typedef struct {
     /* solves whose residual lower bounds (MISOR_TUNE_RES_LITE) missed once: the
      * pass redone counting every cell, the rest of the solve so */
     long long lite_misses;
+    /* the last misor_solve_mg of this grid: cycles run and levels of its
+     * hierarchy; with timing on, the device time of the two transfer kernels
+     * of level 0 ([0] residual + restriction, [1] prolongation + correction),
+     * summed over the solves since the last reset, and the launches it covers
+     * (level 0's smoothing is in sweep_ms like any solve's) */
+    int mg_cycles, mg_levels;
+    double mg_transfer_ms[2];
+    long long mg_transfers;
 } misor_stats;
 
 const char* misor_last_error(void);
@@ -210,6 +218,56 @@ int misor_solve_rb_n(misor_grid* g, int itermax, int* iters, double* res);
  * bounded wait inside the tiled launch gave up; p is then undefined. */
 enum { MISOR_LEX_A4 = 0, MISOR_LEX_SEQ = 1 };
 int misor_solve_lex(misor_grid* g, int xorder, int* iters, double* res);
+
+/* ------------------------------------------------------------ multigrid ---
+ * Geometric multigrid V-cycles for the same problem (lap p = rhs, Neumann by
+ * ghost copy), cell-centred, with the red-black iteration of misor_solve_rb as
+ * smoother and as coarsest-level solver (DESIGN.md "Geometric multigrid" has
+ * the full definition).  Single rank only in this version, variant RB only.
+ *
+ * Levels: level 0 is the grid; level l+1 has (imax/2, jmax/2) cells of
+ * (2dx, 2dy).  Coarsening stops at the first level with an odd side, a side
+ * below 4, or imax*jmax <= coarse_cells: that level is the coarsest.  A grid
+ * that cannot be coarsened has one level and its cycle is the coarsest solve.
+ *
+ * One cycle on a level that is not the coarsest: nu1 solveRB iterations with
+ * omega_smooth (no early exit); r = rhs - lap p; rc = the mean of r over each
+ * coarse cell's four fine cells; e = 0; one cycle on the next level for
+ * lap e = rc; p += the bilinear interpolation of e (weights 9, 3, 3, 1 over
+ * 16, coarse neighbours mirrored at the boundary), then p's ghost copy; nu2
+ * iterations.  The coarsest level runs solveRB with omega_coarse, eps_coarse
+ * and itermax_coarse.
+ *
+ * misor_solve_mg runs cycles while res >= eps^2 (desc.eps) and fewer than
+ * maxcycles are done; res is solveRB's own residual as the last smoothing
+ * iteration on level 0 reports it (post-smoothing; pre-smoothing when nu2 =
+ * 0; the coarsest solve's on a one-level hierarchy), 1.0 before the first
+ * cycle.  desc.omega and desc.itermax are not used, and a later
+ * misor_solve_rb of the grid is what it would have been without this call.
+ * The hierarchy is built by the first call, rebuilt when coarse_cells
+ * changes and freed by misor_destroy. */
+typedef struct {
+    int nu1, nu2;           /* pre- / post-smoothing iterations; nu1 + nu2 >= 1 */
+    double omega_smooth;    /* relaxation factor of the smoothing iterations */
+    int coarse_cells;       /* a level of at most this many cells is not coarsened */
+    double omega_coarse, eps_coarse;  /* the coarsest level's solveRB ... */
+    int itermax_coarse;               /* ... and its cap */
+    int maxcycles;
+} misor_mg_params;
+/* nu1 = nu2 = 2, omega_smooth 1.0, coarse_cells 64, omega_coarse 1.7,
+ * eps_coarse 0.1 * desc.eps, itermax_coarse 1000, maxcycles 100 */
+int misor_mg_default_params(const misor_grid* g, misor_mg_params* out);
+/* host-only: the levels of an imax x jmax grid.  *nlevels = their number;
+ * shapes (2 * cap ints, may be NULL with cap 0) receives {imax, jmax} of the
+ * first min(cap, *nlevels) levels.  MISOR_EINVAL: a side below 2, a negative
+ * coarse_cells or cap, a null nlevels */
+int misor_mg_levels(int imax, int jmax, int coarse_cells, int* nlevels, int* shapes, int cap);
+/* prm NULL: the defaults.  cycles and res may be NULL.  Found before any
+ * device call, in this order: MISOR_EINVAL for a negative nu1 or nu2,
+ * nu1 + nu2 < 1, omega_smooth or omega_coarse not > 0, a negative
+ * coarse_cells, itermax_coarse, maxcycles, a null grid, variant RBA; then
+ * MISOR_ESTATE for a decomposed grid */
+int misor_solve_mg(misor_grid* g, const misor_mg_params* prm, int* cycles, double* res);
 
 /* NS step kernels (assignment-5/sequential/src/solver.c) */
 int misor_ns_setup(misor_grid* g, const misor_ns_desc* ns);

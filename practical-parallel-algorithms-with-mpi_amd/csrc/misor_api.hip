@@ -111,6 +111,7 @@ void misor_destroy(misor_grid* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
+    mg_free(g);  // the multigrid levels (they run on this grid's stream)
     for (auto& f : g->fld)
         if (f) (void)hipFree(f);
     (void)hipFree(g->partials);
@@ -167,7 +168,9 @@ void misor_destroy(misor_grid* g) {
 }
 
 
-int misor_create(misor_grid** out, const misor_desc* d) {
+int misor_create(misor_grid** out, const misor_desc* d) { return grid_create(out, d, false); }
+
+int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
     if (!out || !d) return fail(MISOR_EINVAL, "null argument");
     *out = nullptr;
     if (d->imax < 2 || d->jmax < 2) return fail(MISOR_EINVAL, "imax, jmax must be >= 2");
@@ -233,6 +236,7 @@ int misor_create(misor_grid** out, const misor_desc* d) {
     g->elems = g->pitch * g->rows;
     for (int k = 0; k < kNumFields; ++k) {
         if (k == kP2 && g->np < 3) continue;
+        if (poisson_only && (k == kU || k == kV || k == kF || k == kG)) continue;
         if (hipMalloc(&g->fld[k], (size_t)g->elems * sizeof(double)) != hipSuccess)
             CREATE_FAIL(MISOR_ENOMEM, "hipMalloc of %lld doubles failed", g->elems);
         if (hipMemsetAsync(g->fld[k], 0, (size_t)g->elems * sizeof(double), g->stream) !=
@@ -396,14 +400,18 @@ int misor_set_stream(misor_grid* g, void* s) {
     if (!g) return fail(MISOR_EINVAL, "null grid");
     HIPCHK(hipSetDevice(g->device));
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (g->own_stream) HIPCHK(hipStreamDestroy(g->stream));
-    if (s) {
-        g->stream = (hipStream_t)s;
-        g->own_stream = false;
-    } else {
-        HIPCHK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-        g->own_stream = true;
+    hipStream_t next = (hipStream_t)s;
+    if (!s) HIPCHK(hipStreamCreateWithFlags(&next, hipStreamNonBlocking));
+    // the multigrid levels run on this grid's stream: they move to the new one
+    // while the old one still exists
+    const int rc = mg_set_stream(g, next);
+    if (rc) {
+        if (!s) (void)hipStreamDestroy(next);
+        return rc;
     }
+    if (g->own_stream) HIPCHK(hipStreamDestroy(g->stream));
+    g->stream = next;
+    g->own_stream = !s;
     g->nl.s = g->stream;
     return MISOR_OK;
 }

@@ -226,6 +226,10 @@ struct misor_grid {
     std::vector<hipEvent_t> cev[2];
     size_t cev_used[2] = {0, 0};
 
+    // multigrid (misor_mg.hip): the level hierarchy below this grid, built by
+    // the first misor_solve_mg
+    struct MgHierarchy* mg = nullptr;
+
     // stats
     bool timing = false;
     std::vector<hipEvent_t> ev;
@@ -264,6 +268,9 @@ MISOR_HIDDEN double near_band_rel(int value);
 inline double near_band_abs(double near_rel, double epssq) {
     return near_rel > 0.0 && epssq > 0.0 ? near_rel * epssq : -1.0;
 }
+// misor_create; poisson_only: a grid that only ever solves (a multigrid level)
+// -- the NS fields u, v, f, g are not allocated
+MISOR_HIDDEN int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only);
 MISOR_HIDDEN int grid_adopt(misor_grid* g, const double* p_dev, const double* rhs_dev,
                             double omega, double eps, int itermax);
 
@@ -297,3 +304,8 @@ MISOR_HIDDEN int solve_rb_from(misor_grid* g, int itermax, int it0, double res0,
 
 // misor_ns.hip
 MISOR_HIDDEN int collect_ns_times(misor_grid* g);
+
+// misor_mg.hip
+MISOR_HIDDEN void mg_free(misor_grid* g);
+// the levels below g (if any) onto stream s, which g is about to adopt
+MISOR_HIDDEN int mg_set_stream(misor_grid* g, hipStream_t s);

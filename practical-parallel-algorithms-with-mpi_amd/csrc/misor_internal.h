@@ -316,6 +316,20 @@ void launch_solve_batch(hipStream_t s, double* p_base, const double* rhs_base,
                         long long member_stride, int nbatch, int ni, int nj, long long pitch,
                         double idx2, double idy2, double cells, BatchMember* members);
 
+// multigrid transfers (mg_kernels.hip) between a fine grid and its coarse grid
+// of nic x njc cells (the fine grid has 2 nic x 2 njc): a workgroup covers
+// kMgTileW coarse columns x kMgTileH coarse rows, i.e. a fine tile of
+// 2 kMgTileW x 2 kMgTileH cells
+constexpr int kMgTileW = 256;
+constexpr int kMgTileH = 16;
+// rc = restriction of rhs - lap p (the residual in registers only)
+void launch_mg_residual_restrict(hipStream_t s, const double* p, const double* rhs, double* rc,
+                                 int nic, int njc, long long pitch, long long pitch_c,
+                                 double idx2, double idy2);
+// p += bilinear interpolation of e, then p's ghost copy
+void launch_mg_prolong_correct(hipStream_t s, double* p, const double* e, int nic, int njc,
+                               long long pitch, long long pitch_c);
+
 // 8-neighbour halo exchange of one field (halo.hip): regions in local cell
 // coordinates; direction order L, R, B, T, BL, BR, TL, TR
 constexpr int kDirs = 8;

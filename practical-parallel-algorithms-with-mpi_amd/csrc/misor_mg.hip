@@ -1,0 +1,280 @@
+// misor_mg.hip -- geometric multigrid on top of the red-black solve
+// (include/misor.h "multigrid", DESIGN.md "Geometric multigrid"): the level
+// rule, the hierarchy and the V-cycle.
+//
+// Levels 1 .. L-1 are internal single-rank misor_grids on the user's grid's
+// stream: a level's rhs field is the restricted residual rc of the level
+// above, its current pressure buffer the correction e.  Smoothing and the
+// coarsest solve are misor_solve_rb_n itself, run with other coefficients for
+// the duration of the call (solve_with), so every level takes the kernel the
+// existing rule gives its size -- temporally blocked passes, the single sweep
+// or the whole-solve LDS kernel.  The only kernels of its own are the two
+// transfers of mg_kernels.hip; they add no host round trip to a cycle.
+//
+// Every argument check precedes the first HIP call.
+
+#include "misor_grid.h"
+
+struct MgHierarchy {
+    int coarse_cells = -1;
+    std::vector<misor_grid*> lv;  // lv[0] is the user's grid (not owned)
+    // timing of level 0's transfer kernels (misor_stats.mg_transfer_ms): pair k
+    // is ev[2 * k] (start), ev[2 * k + 1] (stop) around a launch of kind[k]
+    // (0 restriction, 1 prolongation); ev_used pairs are complete
+    std::vector<hipEvent_t> ev;
+    std::vector<int> kind;
+    size_t ev_used = 0;
+};
+
+namespace {
+
+constexpr size_t kMgEventPairs = 64;  // pairs held before they are resolved
+
+// next level's shape, or false where (ni, nj) is the coarsest
+bool mg_coarsen(int ni, int nj, int coarse_cells, int* nic, int* njc) {
+    if ((ni & 1) || (nj & 1) || ni < 4 || nj < 4) return false;
+    if ((long long)ni * nj <= (long long)coarse_cells) return false;
+    *nic = ni / 2;
+    *njc = nj / 2;
+    return true;
+}
+
+int check_params(const misor_mg_params& q) {
+    if (q.nu1 < 0 || q.nu2 < 0)
+        return fail(MISOR_EINVAL, "misor_solve_mg: nu1 = %d, nu2 = %d: counts must be >= 0", q.nu1,
+                    q.nu2);
+    if (q.nu1 + q.nu2 < 1)
+        return fail(MISOR_EINVAL, "misor_solve_mg: nu1 + nu2 must be >= 1 (a cycle smooths)");
+    if (!(q.omega_smooth > 0.0) || !(q.omega_coarse > 0.0))
+        return fail(MISOR_EINVAL, "misor_solve_mg: omega_smooth and omega_coarse must be > 0");
+    if (q.coarse_cells < 0)
+        return fail(MISOR_EINVAL, "misor_solve_mg: coarse_cells = %d must be >= 0",
+                    q.coarse_cells);
+    if (q.itermax_coarse < 0)
+        return fail(MISOR_EINVAL, "misor_solve_mg: itermax_coarse = %d must be >= 0",
+                    q.itermax_coarse);
+    if (q.maxcycles < 0)
+        return fail(MISOR_EINVAL, "misor_solve_mg: maxcycles = %d must be >= 0", q.maxcycles);
+    return MISOR_OK;
+}
+
+misor_mg_params default_params(const misor_grid* g) {
+    misor_mg_params q{};
+    q.nu1 = q.nu2 = 2;
+    q.omega_smooth = 1.0;
+    q.coarse_cells = 64;
+    q.omega_coarse = 1.7;
+    q.eps_coarse = 0.1 * g->desc.eps;
+    q.itermax_coarse = 1000;
+    q.maxcycles = 100;
+    return q;
+}
+
+// solveRB on grid g with relaxation factor omega and tolerance eps instead of
+// the grid's own, capped at itermax; what the solve reads of them (the update
+// coefficient of both sweep geometries, desc.eps) and the batch-size hint are
+// put back before returning, so the grid's next solve is unaffected.
+int solve_with(misor_grid* g, double omega, double eps, int itermax, int* iters, double* res) {
+    const double coef_sp = g->sp.coef, coef_tp = g->tp.coef, eps0 = g->desc.eps;
+    const int last = g->last_iters;
+    g->sp.coef = g->tp.coef = sor_consts(g->desc.dx, g->desc.dy, omega, g->desc.variant).coef;
+    g->desc.eps = eps;
+    const int rc = misor_solve_rb_n(g, itermax, iters, res);
+    g->sp.coef = coef_sp;
+    g->tp.coef = coef_tp;
+    g->desc.eps = eps0;
+    g->last_iters = last;
+    return rc;
+}
+
+// nu iterations without early exit (eps 0: res < 0 never holds); *res only
+// where an iteration ran
+int smooth(misor_grid* g, double omega, int nu, double* res) {
+    if (nu < 1) return MISOR_OK;
+    int it = 0;
+    return solve_with(g, omega, 0.0, nu, &it, res);
+}
+
+void free_levels(MgHierarchy* h) {
+    for (size_t l = 1; l < h->lv.size(); ++l) misor_destroy(h->lv[l]);
+    h->lv.clear();
+}
+
+// (re)build the levels below g for coarse_cells.  A new level comes with a
+// stream of its own and is moved to g's here; misor_set_stream of g moves the
+// levels along (mg_set_stream), so they never hold a stream g has given up.
+int ensure_hierarchy(misor_grid* g, int coarse_cells) {
+    if (!g->mg) g->mg = new MgHierarchy();
+    MgHierarchy* h = g->mg;
+    if (h->coarse_cells != coarse_cells || h->lv.empty()) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        free_levels(h);
+        h->coarse_cells = coarse_cells;
+        h->lv.push_back(g);
+        int ni = g->desc.imax, nj = g->desc.jmax, nic = 0, njc = 0;
+        double dx = g->desc.dx, dy = g->desc.dy;
+        while (mg_coarsen(ni, nj, coarse_cells, &nic, &njc)) {
+            misor_desc d{};
+            d.imax = ni = nic;
+            d.jmax = nj = njc;
+            d.dx = dx = 2.0 * dx;
+            d.dy = dy = 2.0 * dy;
+            d.omega = 1.0;
+            d.variant = MISOR_SOLVE_RB;
+            d.device = g->device;
+            d.nranks = 1;
+            // a level holds e (both pressure buffers) and rc only
+            misor_grid* c = nullptr;
+            const int rc = grid_create(&c, &d, true);
+            if (rc) {
+                free_levels(h);
+                return rc;
+            }
+            h->lv.push_back(c);
+        }
+    }
+    for (size_t l = 1; l < h->lv.size(); ++l)
+        if (h->lv[l]->stream != g->stream) MISOR_TRY(misor_set_stream(h->lv[l], g->stream));
+    return MISOR_OK;
+}
+
+// the timed transfer launches of level 0 so far into the stats
+int collect_transfer_times(misor_grid* g) {
+    MgHierarchy* h = g->mg;
+    if (!h->ev_used) return MISOR_OK;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    for (size_t k = 0; k < h->ev_used; ++k) {
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev[2 * k], h->ev[2 * k + 1]));
+        g->stats.mg_transfer_ms[h->kind[k]] += ms;
+    }
+    g->stats.mg_transfers += (long long)h->ev_used;
+    h->ev_used = 0;
+    return MISOR_OK;
+}
+
+// the start (kind 0 / 1) or stop (kind < 0) event of the next pair around a
+// timed transfer launch, recorded on the stream.  A pair counts once its stop
+// is recorded: a start whose stop never came (an error in between) is reused.
+int record_transfer(misor_grid* g, int kind) {
+    MgHierarchy* h = g->mg;
+    while (h->ev.size() < 2 * kMgEventPairs) {
+        hipEvent_t e;
+        HIPCHK(hipEventCreate(&e));
+        h->ev.push_back(e);
+    }
+    h->kind.resize(kMgEventPairs);
+    const bool stop = kind < 0;
+    if (!stop && h->ev_used == kMgEventPairs) MISOR_TRY(collect_transfer_times(g));
+    if (!stop) h->kind[h->ev_used] = kind;
+    HIPCHK(hipEventRecord(h->ev[2 * h->ev_used + (stop ? 1 : 0)], g->stream));
+    if (stop) ++h->ev_used;
+    return MISOR_OK;
+}
+
+// One cycle on level l; *res: solveRB's residual of the level's last smoothing
+// iteration (the coarsest level: of its solve), untouched if none ran.
+int cycle(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
+    MgHierarchy* h = g0->mg;
+    misor_grid* f = h->lv[l];
+    if (l + 1 == h->lv.size()) {
+        int it = 0;
+        return solve_with(f, q.omega_coarse, q.eps_coarse, q.itermax_coarse, &it, res);
+    }
+    misor_grid* c = h->lv[l + 1];
+    const bool timed = l == 0 && g0->timing;
+    MISOR_TRY(smooth(f, q.omega_smooth, q.nu1, res));
+    // rc = R (rhs - lap p) from the current pressure buffer, into the coarse rhs
+    if (timed) MISOR_TRY(record_transfer(g0, 0));
+    launch_mg_residual_restrict(g0->stream, pbuf(f, f->cur), f->fld[kRhs], c->fld[kRhs],
+                                c->loc.ni, c->loc.nj, f->pitch, c->pitch, f->sp.idx2, f->sp.idy2);
+    HIPCHK(hipGetLastError());
+    if (timed) MISOR_TRY(record_transfer(g0, -1));
+    // e = 0, ghosts included: the cells of the current buffer.  (The other
+    // buffer is written whole -- interior and ghosts -- by the first pass that
+    // uses it; corners and padding are zero in both and never written.)
+    HIPCHK(hipMemset2DAsync(pbuf(c, c->cur) + (long long)kYOff * c->pitch + kXOff,
+                            (size_t)c->pitch * sizeof(double), 0,
+                            (size_t)(c->loc.ni + 2) * sizeof(double), (size_t)c->loc.nj + 2,
+                            g0->stream));
+    double rc_unused = 0.0;
+    MISOR_TRY(cycle(g0, q, l + 1, &rc_unused));
+    if (timed) MISOR_TRY(record_transfer(g0, 1));
+    launch_mg_prolong_correct(g0->stream, pbuf(f, f->cur), pbuf(c, c->cur), c->loc.ni, c->loc.nj,
+                              f->pitch, c->pitch);
+    HIPCHK(hipGetLastError());
+    if (timed) MISOR_TRY(record_transfer(g0, -1));
+    return smooth(f, q.omega_smooth, q.nu2, res);
+}
+
+}  // namespace
+
+void mg_free(misor_grid* g) {
+    if (!g->mg) return;
+    free_levels(g->mg);
+    for (hipEvent_t e : g->mg->ev) (void)hipEventDestroy(e);
+    delete g->mg;
+    g->mg = nullptr;
+}
+
+int mg_set_stream(misor_grid* g, hipStream_t s) {
+    if (!g->mg) return MISOR_OK;
+    for (size_t l = 1; l < g->mg->lv.size(); ++l)
+        MISOR_TRY(misor_set_stream(g->mg->lv[l], s));
+    return MISOR_OK;
+}
+
+int misor_mg_default_params(const misor_grid* g, misor_mg_params* out) {
+    if (!g || !out) return fail(MISOR_EINVAL, "misor_mg_default_params: null argument");
+    *out = default_params(g);
+    return MISOR_OK;
+}
+
+int misor_mg_levels(int imax, int jmax, int coarse_cells, int* nlevels, int* shapes, int cap) {
+    if (!nlevels) return fail(MISOR_EINVAL, "misor_mg_levels: null nlevels");
+    if (imax < 2 || jmax < 2) return fail(MISOR_EINVAL, "misor_mg_levels: imax, jmax must be >= 2");
+    if (coarse_cells < 0 || cap < 0 || (cap > 0 && !shapes))
+        return fail(MISOR_EINVAL, "misor_mg_levels: coarse_cells, cap >= 0; shapes for cap > 0");
+    int n = 0, ni = imax, nj = jmax;
+    for (;;) {
+        if (n < cap) {
+            shapes[2 * n] = ni;
+            shapes[2 * n + 1] = nj;
+        }
+        ++n;
+        int nic = 0, njc = 0;
+        if (!mg_coarsen(ni, nj, coarse_cells, &nic, &njc)) break;
+        ni = nic;
+        nj = njc;
+    }
+    *nlevels = n;
+    return MISOR_OK;
+}
+
+int misor_solve_mg(misor_grid* g, const misor_mg_params* prm, int* cycles, double* res) {
+    if (prm) MISOR_TRY(check_params(*prm));
+    if (!g) return fail(MISOR_EINVAL, "misor_solve_mg: null grid");
+    if (g->desc.variant != MISOR_SOLVE_RB)
+        return fail(MISOR_EINVAL, "misor_solve_mg smooths with solveRB (variant RB)");
+    if (g->dist)
+        return fail(MISOR_ESTATE, "misor_solve_mg has no decomposed form yet (single rank only)");
+    const misor_mg_params q = prm ? *prm : default_params(g);
+    HIPCHK(hipSetDevice(g->device));
+    MISOR_TRY(ensure_hierarchy(g, q.coarse_cells));
+    const double epssq = g->desc.eps * g->desc.eps;
+    int n = 0;
+    double r = 1.0;  // as solveRB's loop (solver.c:196)
+    int rc = MISOR_OK;
+    while ((r >= epssq) && (n < q.maxcycles)) {
+        rc = cycle(g, q, 0, &r);
+        if (rc) break;
+        ++n;
+    }
+    g->stats.mg_cycles = n;
+    g->stats.mg_levels = (int)g->mg->lv.size();
+    if (rc) return rc;
+    MISOR_TRY(collect_transfer_times(g));
+    if (cycles) *cycles = n;
+    if (res) *res = r;
+    return MISOR_OK;
+}

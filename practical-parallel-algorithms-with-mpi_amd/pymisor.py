@@ -70,7 +70,16 @@ class Stats(C.Structure):
                 ("halo_ms", C.c_double), ("halos", C.c_longlong),
                 ("allreduce_ms", C.c_double), ("allreduces", C.c_longlong),
                 ("chained", C.c_int), ("ns_ms", C.c_double * 3), ("ns_calls", C.c_longlong * 3),
-                ("lite_misses", C.c_longlong)]
+                ("lite_misses", C.c_longlong),
+                ("mg_cycles", C.c_int), ("mg_levels", C.c_int),
+                ("mg_transfer_ms", C.c_double * 2), ("mg_transfers", C.c_longlong)]
+
+
+class MgParams(C.Structure):
+    _fields_ = [("nu1", C.c_int), ("nu2", C.c_int), ("omega_smooth", C.c_double),
+                ("coarse_cells", C.c_int), ("omega_coarse", C.c_double),
+                ("eps_coarse", C.c_double), ("itermax_coarse", C.c_int),
+                ("maxcycles", C.c_int)]
 
 
 class Desc3(C.Structure):
@@ -114,6 +123,10 @@ SIGNATURES = {
     "misor_solve_rb": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _dp]),
     "misor_solve_rb_n": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]),
     "misor_solve_lex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]),
+    "misor_mg_default_params": (C.c_int, [C.c_void_p, C.POINTER(MgParams)]),
+    "misor_mg_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int), C.c_int]),
+    "misor_solve_mg": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.POINTER(C.c_int), _dp]),
     "misor_ns_setup": (C.c_int, [C.c_void_p, C.POINTER(NsDesc)]),
     "misor_compute_timestep": (C.c_int, [C.c_void_p, C.c_double, C.c_double, _dp]),
     "misor_set_dt": (C.c_int, [C.c_void_p, C.c_double]),
@@ -218,6 +231,16 @@ def decompose(nranks, rank, imax, jmax, dims=(0, 0)):
     return loc
 
 
+def mg_levels(imax, jmax, coarse_cells=64):
+    """[(imax, jmax), ...] of the multigrid levels of an imax x jmax grid, level 0
+    first (misor_mg_levels; host-only)"""
+    n = C.c_int(0)
+    _check(lib().misor_mg_levels(imax, jmax, coarse_cells, C.byref(n), None, 0))
+    shapes = (C.c_int * (2 * n.value))()
+    _check(lib().misor_mg_levels(imax, jmax, coarse_cells, C.byref(n), shapes, n.value))
+    return [(shapes[2 * k], shapes[2 * k + 1]) for k in range(n.value)]
+
+
 def comm_unique_id() -> bytes:
     buf = C.create_string_buffer(COMM_ID_BYTES)
     _check(lib().misor_comm_unique_id(buf))
@@ -308,6 +331,26 @@ class Grid:
         _check(lib().misor_solve_lex(self.h, xorder, C.byref(it), C.byref(res)))
         return it.value, res.value
 
+    def mg_default_params(self):
+        q = MgParams()
+        _check(lib().misor_mg_default_params(self.h, C.byref(q)))
+        return q
+
+    def solve_mg(self, **params):
+        """multigrid V-cycles (misor_solve_mg): (cycles, res).  Keywords are
+        the fields of misor_mg_params (nu1, nu2, omega_smooth, coarse_cells,
+        omega_coarse, eps_coarse, itermax_coarse, maxcycles); those not given
+        keep their defaults"""
+        q = self.mg_default_params()
+        names = [f[0] for f in MgParams._fields_]
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError("solve_mg: unknown parameter %r (one of %s)" % (k, names))
+            setattr(q, k, v)
+        n, res = C.c_int(0), C.c_double(0.0)
+        _check(lib().misor_solve_mg(self.h, C.byref(q), C.byref(n), C.byref(res)))
+        return n.value, res.value
+
     def synchronize(self):
         _check(lib().misor_synchronize(self.h))
 
@@ -371,7 +414,9 @@ class Grid:
                 "halo_ms": s.halo_ms, "halos": s.halos,
                 "allreduce_ms": s.allreduce_ms, "allreduces": s.allreduces,
                 "chained": s.chained, "ns_ms": list(s.ns_ms), "ns_calls": list(s.ns_calls),
-                "lite_misses": s.lite_misses}
+                "lite_misses": s.lite_misses, "mg_cycles": s.mg_cycles,
+                "mg_levels": s.mg_levels, "mg_transfer_ms": list(s.mg_transfer_ms),
+                "mg_transfers": s.mg_transfers}
 
     def reset_stats(self):
         _check(lib().misor_reset_stats(self.h))
