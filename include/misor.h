@@ -535,6 +535,61 @@ int misor3_set_tuning(misor_grid3* g, int key, int value);
 int misor3_get_tuning(const misor_grid3* g, int key, int* value);
 int misor3_get_solve_time(const misor_grid3* g, double* ms, long long* iters);
 
+/* --- 3D multigrid: the V-cycle of misor_solve_mg above for lap p = rhs on one
+ * misor_grid3 (DESIGN.md "Geometric multigrid, 3D" has the full definition).
+ * Neumann by misor3_solve's ghost copy (faces only); smoother and coarsest
+ * solver are misor3_solve's red-black iteration.  Single rank only.
+ *
+ * Levels: level l+1 has (imax/2, jmax/2, kmax/2) cells of (2dx, 2dy, 2dz);
+ * the coarsest is the first with an odd side, a side below 4, or
+ * imax*jmax*kmax <= coarse_cells.
+ *
+ * A cycle on a level that is not the coarsest: nu1 iterations with
+ * omega_smooth (no early exit); r = rhs - lap p in the solve's own expression;
+ * rc = the mean of r over a coarse cell's eight fine cells; e = 0; a cycle on
+ * the next level for lap e = rc; p += the trilinear interpolation of e
+ * (weights 27, 9, 3, 1 over 64, coarse neighbours mirrored at the boundary),
+ * then p's ghost copy; nu2 iterations.  The coarsest level runs the solve's
+ * loop with omega_coarse, eps_coarse, itermax_coarse, its residual carry
+ * seeded with 1.0 like misor3_solve's.  The reference carries res from one
+ * iteration into the next (res <- (res + sum r^2) / N), so nu iterations
+ * seeded with 1.0 cannot report less than N^-nu: smoothing calls seed the
+ * carry with 0.0.
+ *
+ * misor3_solve_mg runs cycles while res >= eps^2 (desc.eps) and fewer than
+ * maxcycles are done; res is what the last smoothing call on level 0 leaves
+ * (post-smoothing; pre-smoothing when nu2 = 0; the coarsest solve's on a
+ * one-level hierarchy), 1.0 before the first cycle.  desc.omega and
+ * desc.itermax are not used, and a later misor3_solve is what it would have
+ * been without this call.  The MISOR3_TUNE_* knobs apply to level 0 only.  The
+ * hierarchy is built by the first call, rebuilt when coarse_cells changes and
+ * freed by misor3_destroy. */
+/* nu1 = nu2 = 2, omega_smooth 1.0, coarse_cells 512, omega_coarse 1.7,
+ * eps_coarse 0.1 * desc.eps, itermax_coarse 1000, maxcycles 100 */
+int misor3_mg_default_params(const misor_grid3* g, misor_mg_params* out);
+/* host-only: the levels of an imax x jmax x kmax grid.  *nlevels = their
+ * number; shapes (3 * cap ints, may be NULL with cap 0) receives {imax, jmax,
+ * kmax} of the first min(cap, *nlevels) levels.  MISOR_EINVAL: a side below 2,
+ * a negative coarse_cells or cap, a null nlevels */
+int misor3_mg_levels(int imax, int jmax, int kmax, int coarse_cells, int* nlevels, int* shapes,
+                     int cap);
+/* prm NULL: the defaults.  cycles and res may be NULL.  Found before any
+ * device call, in this order: MISOR_EINVAL for bad parameters (as
+ * misor_solve_mg's) or a null grid; then MISOR_ESTATE for a decomposed grid,
+ * slabs or Cartesian */
+int misor3_solve_mg(misor_grid3* g, const misor_mg_params* prm, int* cycles, double* res);
+/* the last misor3_solve_mg of this grid: cycles run and levels of its
+ * hierarchy; while misor3_enable_timing is on, the device time of level 0's
+ * two transfer kernels ([0] residual + restriction, [1] prolongation +
+ * correction + ghost copy) and the launches it covers, summed since timing was
+ * enabled (level 0's smoothing is in misor3_get_solve_time) */
+typedef struct {
+    int cycles, levels;
+    double transfer_ms[2];
+    long long transfers;
+} misor3_mg_info;
+int misor3_get_mg_info(const misor_grid3* g, misor3_mg_info* out);
+
 /* --- the box over a 3D Cartesian process grid (assignment-6/src/comm.c:24-101,
  * 476-513), a second decomposition beside the slabs.  A rank owns a block of
  * {ni, nj, nk} cells; its local array is the reference's, (ni+2)(nj+2)(nk+2)

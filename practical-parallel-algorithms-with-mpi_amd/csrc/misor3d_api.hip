@@ -39,13 +39,10 @@
 #include <string>
 #include <vector>
 
-#include "misor_internal.h"
+#include "misor_grid3.h"
 
 using namespace misor;
 
-namespace {
-
-int fail3(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 int fail3(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -56,13 +53,7 @@ int fail3(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIPCHK3(x)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (x);                                                               \
-        if (e_ != hipSuccess)                                                              \
-            return fail3(MISOR_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                        \
-    } while (0)
+namespace {
 
 #define NCCLCHK3(x)                                                                        \
     do {                                                                                   \
@@ -72,67 +63,11 @@ int fail3(int code, const char* fmt, ...) {
                          __FILE__, __LINE__);                                              \
     } while (0)
 
-constexpr int kHalo = 2;          // halo planes per side in storage
-constexpr int kSlack = 2;         // spare doubles before / after every buffer: the sweep's
-                                  // 16-byte column-pair loads reach one past a row end
-constexpr int kBufs = 9;          // the 8 fields + the ping-pong partner of P
-constexpr int kAlt = 8;
 constexpr char kLocalPrefix3[] = "LOCAL:";
 
 int size_of_rank3(int rank, int size, int n) { return n / size + ((n % size > rank) ? 1 : 0); }
 
-struct LocalGroup3;
-
 }  // namespace
-
-struct misor_grid3 {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    misor3_desc desc{};
-    G3 g{};                    // this rank's slab: g.K planes, g.koff, physical flags
-    long long n = 0;           // cells of the reference's local array (planes 0 .. K+1)
-    long long nalloc = 0;      // cells allocated per field (planes -1 .. K+2)
-    double* alloc[kBufs] = {}; // allocations: nalloc + 2*kSlack doubles
-    double* mem[kBufs] = {};   // plane -1 of each buffer (alloc + kSlack)
-    double* fld[kBufs] = {};   // plane-0 origins: MISOR3_P .. MISOR3_H, kAlt = P's partner
-    bool alt_stale = true;     // the partner's edge/corner ghosts may differ from P's
-    int sweep = 1;             // MISOR3_TUNE_SWEEP
-    int rows = 8;              // MISOR3_TUNE_ROWS
-    int kchunk = 0;            // MISOR3_TUNE_KCHUNK (0: automatic)
-    int fold = 1;              // MISOR3_TUNE_FOLD: single rank, loop test inside the sweep
-    int resident = -1;         // MISOR3_TUNE_RESIDENT: whole solve in one launch when it fits
-    void* rbar = nullptr;      // its grid-barrier state and partials, uncached memory
-    double* rmbox = nullptr;   // its exchange mailboxes (2 x p's layout), uncached memory
-    int rhs_ahead = 0;         // MISOR3_TUNE_RHS_AHEAD: fused sweep's rhs loads 1 or 2 steps
-                               // ahead; 0: 2 on marches of >= 16 planes, else 1
-    double dx = 0, dy = 0, dz = 0, dt = 0, dt_bound = 0;
-    double* partials = nullptr;  // per-block partial sums / maxima
-    long long partials_cap = 0;
-    double* out = nullptr;      // 4 doubles on the device (maxima / sum)
-    double* out_host = nullptr; // pinned
-    DevState* st = nullptr;
-    DevState* st2 = nullptr;  // the folded loop test's second state buffer
-    DevState* st_host = nullptr;
-    int last_iters = 0;
-    bool timing = false;          // misor3_enable_timing
-    hipEvent_t ev[2] = {};        // around each solve, on the grid's stream
-    double solve_ms = 0;          // accumulated device time of timed solves
-    long long solve_iters = 0;    // iterations of the timed solves
-    // decomposition
-    int nranks = 1, rank = 0, prev = -1, next = -1;
-    ncclComm_t comm = nullptr;
-    std::shared_ptr<LocalGroup3> local;
-    double* gstage = nullptr;     // rank 0: receive staging of misor3_gather (RCCL)
-    // Cartesian process grid (misor3_create_cart)
-    bool cart = false;
-    misor3_local loc{};
-    double* hbuf = nullptr;       // staging of the x / y faces, one allocation
-    double* hsend[4] = {};        // left, right, bottom, top: packed owned layer
-    double* hrecv[4] = {};        // the neighbour's, before it is unpacked into the ghost layer
-    double* gbuf = nullptr;       // the box this rank contributes to misor3_gather
-};
-
-namespace {
 
 // In-process transport (as in 2D, misor_api.hip): the ranks are grids driven
 // by host threads of one process; collectives are a host barrier plus
@@ -157,6 +92,9 @@ struct LocalGroup3 {
         }
     }
 };
+
+namespace {
+
 std::mutex g_groups3_mu;
 std::map<std::string, std::shared_ptr<LocalGroup3>> g_groups3;
 
@@ -436,6 +374,7 @@ void misor3_destroy(misor_grid3* g) {
     if (!g) return;
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
+    mg3_free(g);  // the multigrid levels (they run on this grid's stream)
     for (auto& f : g->alloc)
         if (f) (void)hipFree(f);
     (void)hipFree(g->partials);
@@ -452,7 +391,7 @@ void misor3_destroy(misor_grid3* g) {
     for (auto& e : g->ev)
         if (e) (void)hipEventDestroy(e);
     if (g->comm) ncclCommDestroy(g->comm);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
+    if (g->stream && g->own_stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
 
@@ -507,8 +446,10 @@ int misor3_decompose_cart(int nranks, int rank, const int dims_in[3], int imax, 
     return MISOR_OK;
 }
 
-// misor3_create (dims == nullptr: slabs) and misor3_create_cart
-static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, bool cart) {
+// misor3_create (dims == nullptr: slabs) and misor3_create_cart; level_stream:
+// create3_level's grid on that stream, with p, its partner and rhs only
+static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, bool cart,
+                   hipStream_t level_stream = nullptr) {
     if (!out || !d) return fail3(MISOR_EINVAL, "null argument");
     *out = nullptr;
     if (d->imax < 2 || d->jmax < 2 || d->kmax < 2)
@@ -551,8 +492,12 @@ static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, boo
         misor3_destroy(g);                   \
         return c_;                           \
     } while (0)
-    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess)
+    if (level_stream) {
+        g->stream = level_stream;
+        g->own_stream = false;
+    } else if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
         CF(MISOR_EHIP, "hipStreamCreate failed");
+    }
     g->g.I = iloc;
     g->g.J = jloc;
     g->g.K = kloc;
@@ -587,6 +532,7 @@ static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, boo
         g->dt_bound = 0.5 * d->re * 1.0 / inv;  // solver.c:136-139
     }
     for (int b = 0; b < kBufs; ++b) {
+        if (level_stream && b != MISOR3_P && b != MISOR3_RHS && b != kAlt) continue;
         const size_t bytes = sizeof(double) * (size_t)(g->nalloc + 2 * kSlack);
         if (hipMalloc(&g->alloc[b], bytes) != hipSuccess)
             CF(MISOR_ENOMEM, "hipMalloc of %lld doubles failed", g->nalloc);
@@ -663,6 +609,31 @@ int misor3_create(misor_grid3** out, const misor3_desc* d) {
 int misor3_create_cart(misor_grid3** out, const misor3_desc* d, const int dims[3]) {
     return create3(out, d, dims, true);
 }
+
+}  // extern "C"
+
+int create3_level(misor_grid3** out, const misor3_desc* d, hipStream_t s) {
+    return create3(out, d, nullptr, false, s);
+}
+
+int solve3_with(misor_grid3* g, double omega, double eps, int itermax, double res_seed,
+                int* iters, double* res) {
+    const double omega0 = g->desc.omega, eps0 = g->desc.eps;
+    const int itermax0 = g->desc.itermax, last = g->last_iters;
+    g->desc.omega = omega;
+    g->desc.eps = eps;
+    g->desc.itermax = itermax;
+    g->res_seed = res_seed;
+    const int rc = misor3_solve(g, iters, res);
+    g->desc.omega = omega0;
+    g->desc.eps = eps0;
+    g->desc.itermax = itermax0;
+    g->res_seed = 1.0;
+    g->last_iters = last;
+    return rc;
+}
+
+extern "C" {
 
 int misor3_local_info(const misor_grid3* g, int* kloc, int* koff) {
     if (!g) return fail3(MISOR_EINVAL, "null grid");
@@ -973,13 +944,13 @@ int misor3_solve(misor_grid3* g, int* iters, double* res) {
     const double factor = d.omega * 0.5 * (dx2 * dy2 * dz2) / (dy2 * dz2 + dx2 * dz2 + dx2 * dy2);
     const double cells = (double)((long long)d.imax * d.jmax * d.kmax);
     DevState s0{};
-    s0.res = 1.0;
+    s0.res = g->res_seed;  // 1.0 (solver.c:196) outside solve3_with
     s0.epssq = d.eps * d.eps;
     s0.itermax = d.itermax;
     s0.done = !((s0.res >= s0.epssq) && (0 < d.itermax));
     if (s0.done) {
         if (iters) *iters = 0;
-        if (res) *res = 1.0;
+        if (res) *res = s0.res;
         return MISOR_OK;
     }
     if (g->cart) {
@@ -1234,6 +1205,8 @@ int misor3_enable_timing(misor_grid3* g, int on) {
     g->timing = on != 0;
     g->solve_ms = 0;
     g->solve_iters = 0;
+    g->mg_info.transfer_ms[0] = g->mg_info.transfer_ms[1] = 0;
+    g->mg_info.transfers = 0;
     return MISOR_OK;
 }
 

@@ -500,4 +500,19 @@ void launch3_fold_decide(hipStream_t s, const G3& g, int rows, int kc,
                          const double* prev_partials, const DevState* st_in, DevState* st_out,
                          double cells);
 
+// 3D multigrid transfers (mg3_kernels.hip) between a fine grid f and its
+// coarse grid c (f has 2 c.I x 2 c.J x 2 c.K cells), both single-domain: a
+// workgroup covers kMg3TileW coarse columns x kMg3TileH coarse rows and marches
+// kMg3TileD coarse planes, i.e. a fine box of twice that each way
+constexpr int kMg3TileW = 64;
+constexpr int kMg3TileH = 8;
+constexpr int kMg3TileD = 8;
+// rc = restriction of rhs - lap p (the residual in registers only)
+void launch_mg3_residual_restrict(hipStream_t s, const G3& f, const G3& c, const double* p,
+                                  const double* rhs, double* rc, double idx2, double idy2,
+                                  double idz2);
+// p += trilinear interpolation of e, then the ghost copy of p's faces
+void launch_mg3_prolong_correct(hipStream_t s, const G3& f, const G3& c, double* p,
+                                const double* e);
+
 }  // namespace misor

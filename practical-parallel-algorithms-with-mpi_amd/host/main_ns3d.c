@@ -11,6 +11,9 @@
  * MISOR_DIMS=XxYxZ splits the box over that 3D Cartesian process grid instead
  * of slabs, as the reference's MPI_Dims_create / MPI_Cart_create does (a 0
  * entry is chosen automatically: MISOR_DIMS=0x0x0 with 8 ranks is 2x2x2).
+ * MISOR_PSOLVE=mg replaces the step's red-black SOR by multigrid V-cycles
+ * (misor3_solve_mg, default parameters; single rank only) and prints one line
+ * naming the solver; unset or "sor" is the reference's solve.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -105,8 +108,16 @@ int main(int argc, char** argv)
     readParameter(&p, argv[1]);
     int dims[3];
     (void)rankDims(dims); /* a malformed MISOR_DIMS ends the program here, before any rank starts */
+    /* MISOR_PSOLVE: a bad value, or mg on more than one rank, ends the program
+     * here, before any rank starts */
+    const char* nr = getenv("MISOR_RANKS");
+    const char* ws = getenv("WORLD_SIZE");
+    const int ranks = nr ? atoi(nr) : (ws ? atoi(ws) : 1);
+    const int psolve = pressureSolver(ranks);
     const char* r = getenv("RANK");
     if (!r || atoi(r) == 0) printParameter3D(&p);
+    if (psolve == PSOLVE_MG)
+        printf("Pressure solver: geometric multigrid V-cycles (misor3_solve_mg)\n");
     fflush(stdout);
     return runRanks(rank_main, &p) ? EXIT_FAILURE : EXIT_SUCCESS;
 }

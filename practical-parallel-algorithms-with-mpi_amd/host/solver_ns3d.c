@@ -21,6 +21,23 @@ static int problemId(const char* name)
     return MISOR_PROBLEM_NONE;
 }
 
+int pressureSolver(int ranks)
+{
+    const char* v = getenv("MISOR_PSOLVE");
+    if (!v || strcmp(v, "sor") == 0) return PSOLVE_SOR;
+    if (strcmp(v, "mg") != 0) {
+        fprintf(stderr, "MISOR_PSOLVE=%s: unknown pressure solver (sor or mg)\n", v);
+        exit(EXIT_FAILURE);
+    }
+    if (ranks > 1) {
+        fprintf(stderr,
+            "MISOR_PSOLVE=mg: the multigrid pressure solve is single rank only (%d ranks asked for)\n",
+            ranks);
+        exit(EXIT_FAILURE);
+    }
+    return PSOLVE_MG;
+}
+
 /* initSolver, solver.c:75-143 */
 void initSolver(Solver* s, Parameter* params)
 {
@@ -86,6 +103,7 @@ void initSolver(Solver* s, Parameter* params)
     d.comm_id = rk->comm_id;
     s->rank = rk->rank;
     s->size = rk->size;
+    s->psolve = pressureSolver(rk->size);
     int dims[3];
     if (rk->size > 1 && rankDims(dims))
         misorCheck(misor3_create_cart(&s->dev, &d, dims), "initSolver");
@@ -106,7 +124,10 @@ void computeRHS(Solver* s) { misorCheck(misor3_compute_rhs(s->dev), "computeRHS"
 
 void solve(Solver* s)
 {
-    misorCheck(misor3_solve(s->dev, &s->lastIterations, &s->lastRes), "solve");
+    if (s->psolve == PSOLVE_MG) /* lastIterations: V-cycles */
+        misorCheck(misor3_solve_mg(s->dev, NULL, &s->lastIterations, &s->lastRes), "solve");
+    else
+        misorCheck(misor3_solve(s->dev, &s->lastIterations, &s->lastRes), "solve");
 #ifdef VERBOSE
     if (s->rank == 0)
         printf("Solver took %d iterations to reach %f\n", s->lastIterations, sqrt(s->lastRes));

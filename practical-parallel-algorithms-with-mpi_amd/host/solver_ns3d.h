@@ -32,7 +32,15 @@ typedef struct {
     int lastIterations; /* iterations of the last pressure solve (added) */
     double lastRes;     /* its final residual (added) */
     int rank, size;     /* this rank of a decomposed run (added; 0 of 1 on one GPU) */
+    int psolve;         /* PSOLVE_* (added): what solve() runs */
 } Solver;
+
+/* MISOR_PSOLVE: unset or "sor" = the reference's red-black SOR (misor3_solve),
+ * "mg" = multigrid V-cycles with the default parameters (misor3_solve_mg,
+ * single rank only).  pressureSolver() ends the program with a message on any
+ * other value, and on "mg" where `ranks` > 1 */
+enum { PSOLVE_SOR = 0, PSOLVE_MG = 1 };
+extern int pressureSolver(int ranks);
 
 extern void initSolver(Solver*, Parameter*);
 extern void computeRHS(Solver*);

@@ -75,6 +75,11 @@ class Stats(C.Structure):
                 ("mg_transfer_ms", C.c_double * 2), ("mg_transfers", C.c_longlong)]
 
 
+class MgInfo3(C.Structure):
+    _fields_ = [("cycles", C.c_int), ("levels", C.c_int), ("transfer_ms", C.c_double * 2),
+                ("transfers", C.c_longlong)]
+
+
 class MgParams(C.Structure):
     _fields_ = [("nu1", C.c_int), ("nu2", C.c_int), ("omega_smooth", C.c_double),
                 ("coarse_cells", C.c_int), ("omega_coarse", C.c_double),
@@ -184,6 +189,11 @@ SIGNATURES = {
                                      C.POINTER(C.c_int)]),
     "misor3_local_info_cart": (C.c_int, [C.c_void_p, C.POINTER(Local3)]),
     "misor3_exchange": (C.c_int, [C.c_void_p, C.c_int]),
+    "misor3_mg_default_params": (C.c_int, [C.c_void_p, C.POINTER(MgParams)]),
+    "misor3_mg_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_int), C.c_int]),
+    "misor3_solve_mg": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.POINTER(C.c_int), _dp]),
+    "misor3_get_mg_info": (C.c_int, [C.c_void_p, C.POINTER(MgInfo3)]),
 }
 
 _lib = None
@@ -239,6 +249,16 @@ def mg_levels(imax, jmax, coarse_cells=64):
     shapes = (C.c_int * (2 * n.value))()
     _check(lib().misor_mg_levels(imax, jmax, coarse_cells, C.byref(n), shapes, n.value))
     return [(shapes[2 * k], shapes[2 * k + 1]) for k in range(n.value)]
+
+
+def mg3_levels(imax, jmax, kmax, coarse_cells=512):
+    """[(imax, jmax, kmax), ...] of the 3D multigrid levels, level 0 first
+    (misor3_mg_levels; host-only)"""
+    n = C.c_int(0)
+    _check(lib().misor3_mg_levels(imax, jmax, kmax, coarse_cells, C.byref(n), None, 0))
+    shapes = (C.c_int * (3 * n.value))()
+    _check(lib().misor3_mg_levels(imax, jmax, kmax, coarse_cells, C.byref(n), shapes, n.value))
+    return [tuple(shapes[3 * k:3 * k + 3]) for k in range(n.value)]
 
 
 def comm_unique_id() -> bytes:
@@ -650,6 +670,34 @@ class Grid3:
         v = C.c_int(0)
         _check(lib().misor3_get_tuning(self.h, key, C.byref(v)))
         return v.value
+
+    def mg_default_params(self):
+        """nu1 = nu2 = 2, omega_smooth 1.0, coarse_cells 512, omega_coarse 1.7,
+        eps_coarse 0.1 eps, itermax_coarse 1000, maxcycles 100"""
+        q = MgParams()
+        _check(lib().misor3_mg_default_params(self.h, C.byref(q)))
+        return q
+
+    def solve_mg(self, **params):
+        """multigrid V-cycles (misor3_solve_mg): (cycles, res).  Keywords are
+        the fields of misor_mg_params; those not given keep their 3D defaults"""
+        q = self.mg_default_params()
+        names = [f[0] for f in MgParams._fields_]
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError("solve_mg: unknown parameter %r (one of %s)" % (k, names))
+            setattr(q, k, v)
+        n, res = C.c_int(0), C.c_double(0.0)
+        _check(lib().misor3_solve_mg(self.h, C.byref(q), C.byref(n), C.byref(res)))
+        return n.value, res.value
+
+    def mg_info(self):
+        """the last solve_mg: cycles, levels; with timing on the device ms of
+        level 0's two transfer kernels and the launches they cover"""
+        s = MgInfo3()
+        _check(lib().misor3_get_mg_info(self.h, C.byref(s)))
+        return {"cycles": s.cycles, "levels": s.levels, "transfer_ms": list(s.transfer_ms),
+                "transfers": s.transfers}
 
     def solve_time(self):
         """(device ms, iterations) of the solves timed since enable_timing"""
