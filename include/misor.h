@@ -137,6 +137,18 @@ typedef struct {
     int mg_cycles, mg_levels;
     double mg_transfer_ms[2];
     long long mg_transfers;
+    /* the fused tail (misor_mg_tail, MISOR_TUNE_MG_TAIL): levels the last
+     * misor_solve_mg cycled in one launch (0: none -- the tail has fewer than
+     * two levels, the knob is off, or no cycle ran); its launches, and the
+     * cycles the host finished level by level because the coarsest solve came
+     * near its threshold, both since the last reset; with timing on, the device
+     * time of those launches.  The iterations the fused levels run are in no
+     * other counter: where level 0 is in the tail, sweeps and sweep_ms do not
+     * count its smoothing */
+    int mg_tail_levels;
+    long long mg_tail_launches;
+    long long mg_tail_fallbacks;
+    double mg_tail_ms;
 } misor_stats;
 
 const char* misor_last_error(void);
@@ -245,7 +257,13 @@ int misor_solve_lex(misor_grid* g, int xorder, int* iters, double* res);
  * cycle.  desc.omega and desc.itermax are not used, and a later
  * misor_solve_rb of the grid is what it would have been without this call.
  * The hierarchy is built by the first call, rebuilt when coarse_cells
- * changes and freed by misor_destroy. */
+ * changes and freed by misor_destroy.  The levels' solves test their loops as
+ * the grid's own do (MISOR_TUNE_NEAR_BAND of the grid holds on every level).
+ *
+ * The tail of the hierarchy -- its trailing levels that each fit the LDS of one
+ * workgroup, misor_mg_tail -- is cycled by one launch a cycle instead of two
+ * solves a level, and a grid that itself fits is solved, loop over the cycles
+ * included, in one launch (MISOR_TUNE_MG_TAIL; the same bits either way). */
 typedef struct {
     int nu1, nu2;           /* pre- / post-smoothing iterations; nu1 + nu2 >= 1 */
     double omega_smooth;    /* relaxation factor of the smoothing iterations */
@@ -262,6 +280,17 @@ int misor_mg_default_params(const misor_grid* g, misor_mg_params* out);
  * first min(cap, *nlevels) levels.  MISOR_EINVAL: a side below 2, a negative
  * coarse_cells or cap, a null nlevels */
 int misor_mg_levels(int imax, int jmax, int coarse_cells, int* nlevels, int* shapes, int cap);
+/* host-only: the tail of the hierarchy misor_mg_levels gives for these
+ * arguments -- its maximal run of trailing levels that each fit the LDS of one
+ * workgroup (the rule of MISOR_TUNE_SMALL_SOLVE: (imax+2)(jmax+2) doubles and
+ * 256 bytes within 160 KB, and at most 8192 cell pairs jmax * ceil(imax/2)).
+ * *first = index of the first level held in LDS, *count = levels in the tail
+ * (0: none fits, then *first = nlevels).  A tail of two or more levels is
+ * cycled by one kernel launch a cycle, one workgroup walking the levels down
+ * and up in LDS; where *first = 0 the whole misor_solve_mg is one launch and
+ * one read-back of its state (MISOR_TUNE_MG_TAIL).  Same MISOR_EINVAL cases as
+ * misor_mg_levels, and a null first or count. */
+int misor_mg_tail(int imax, int jmax, int coarse_cells, int* first, int* count);
 /* prm NULL: the defaults.  cycles and res may be NULL.  Found before any
  * device call, in this order: MISOR_EINVAL for a negative nu1 or nu2,
  * nu1 + nu2 < 1, omega_smooth or omega_coarse not > 0, a negative
@@ -370,7 +399,13 @@ enum {
                                     * holds resident.  Progress needs no residency: 1
                                     * runs the tiles one after the other.  p and the
                                     * iteration count are the same bits for every value
-                                    * (res too) */
+                                    * (res too) */,
+    MISOR_TUNE_MG_TAIL = 21        /* misor_solve_mg: 1 (default) = the tail of the
+                                    * hierarchy (misor_mg_tail) is cycled in one launch
+                                    * when it has two or more levels; 0 = every level by
+                                    * its own launches.  Get returns the setting.  p, the
+                                    * cycle count and res are the same bits for either
+                                    * value */
 };
 int misor_set_tuning(misor_grid* g, int key, int value);
 int misor_get_tuning(const misor_grid* g, int key, int* value);

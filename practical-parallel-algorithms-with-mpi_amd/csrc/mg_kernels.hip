@@ -16,6 +16,7 @@
 // the composed numpy oracle of tests/test_mg_gpu.py matches bit for bit.
 
 #include "misor_internal.h"
+#include "mg_transfer.h"
 
 namespace misor {
 
@@ -28,14 +29,10 @@ __device__ __forceinline__ void st2(double* p, double a, double b) {
     *reinterpret_cast<double2*>(p) = make_double2(a, b);
 }
 
-// solveRB's residual of one cell: centre c, west / east / south / north
-__device__ __forceinline__ double resid(double rhs, double c, double w, double e, double s,
-                                        double n, double idx2, double idy2) {
-    return rhs - ((e - 2.0 * c + w) * idx2 + (n - 2.0 * c + s) * idy2);
-}
-
 // rc(I,J) = 0.25 ((r(2I-1,2J-1) + r(2I,2J-1)) + (r(2I-1,2J) + r(2I,2J))),
-// r = rhs - lap p.  The four residuals live in registers only.  Per fine row
+// r = rhs - lap p; the expressions are mg_transfer.h's, shared with the
+// LDS-resident cycle of mg_tail.hip.  The four residuals live in registers
+// only.  Per fine row
 // a thread loads its pair of p (16 B), the two x-neighbours (8 B each, L1)
 // and its pair of rhs; a fine row of p is loaded once and kept while the
 // march needs it (south of, in, north of the row pair), so a workgroup reads
@@ -63,11 +60,11 @@ __global__ __launch_bounds__(kMgTileW) void mg_residual_restrict_kernel(
         const double2 n = ld2(p + rn);  // row 2J+1: north of the pair, first row of the next
         const double2 fa = ld2(rhs + row(2 * J - 1));
         const double2 fb = ld2(rhs + rb);
-        const double r00 = resid(fa.x, a.x, aw, a.y, sx, b.x, idx2, idy2);
-        const double r10 = resid(fa.y, a.y, a.x, ae, sy, b.y, idx2, idy2);
-        const double r01 = resid(fb.x, b.x, bw, b.y, a.x, n.x, idx2, idy2);
-        const double r11 = resid(fb.y, b.y, b.x, be, a.y, n.y, idx2, idy2);
-        rc[(long long)(J + kYOff) * pitch_c + I + kXOff] = 0.25 * ((r00 + r10) + (r01 + r11));
+        const double r00 = mg_resid(fa.x, a.x, aw, a.y, sx, b.x, idx2, idy2);
+        const double r10 = mg_resid(fa.y, a.y, a.x, ae, sy, b.y, idx2, idy2);
+        const double r01 = mg_resid(fb.x, b.x, bw, b.y, a.x, n.x, idx2, idy2);
+        const double r11 = mg_resid(fb.y, b.y, b.x, be, a.y, n.y, idx2, idy2);
+        rc[(long long)(J + kYOff) * pitch_c + I + kXOff] = mg_restrict4(r00, r10, r01, r11);
         if (J < J1) {
             sx = b.x;
             sy = b.y;
@@ -107,10 +104,10 @@ __global__ __launch_bounds__(kMgTileW) void mg_prolong_correct_kernel(
         const long long ra = row(2 * J - 1), rb = row(2 * J);
         const double2 a = ld2(p + ra), b = ld2(p + rb);
         // row 2J-1 (sy = -1): columns 2I-1 (sx = -1) and 2I (sx = +1); row 2J (sy = +1)
-        const double a0 = a.x + (9.0 * mc + 3.0 * (mw + sc) + sw) * 0.0625;
-        const double a1 = a.y + (9.0 * mc + 3.0 * (me + sc) + se) * 0.0625;
-        const double b0 = b.x + (9.0 * mc + 3.0 * (mw + nc) + nw) * 0.0625;
-        const double b1 = b.y + (9.0 * mc + 3.0 * (me + nc) + ne) * 0.0625;
+        const double a0 = a.x + mg_interp(mc, mw, sc, sw);
+        const double a1 = a.y + mg_interp(mc, me, sc, se);
+        const double b0 = b.x + mg_interp(mc, mw, nc, nw);
+        const double b1 = b.y + mg_interp(mc, me, nc, ne);
         st2(p + ra, a0, a1);
         st2(p + rb, b0, b1);
         // the ghost copy (solver.c:218-226): columns 0 and ni + 1, rows 0 and nj + 1

@@ -816,6 +816,10 @@ int misor_set_tuning(misor_grid* g, int key, int value) {
         return MISOR_OK;
     }
     case MISOR_TUNE_LEX_WGS: g->lex_wgs = value > 0 ? value : 0; return MISOR_OK;
+    case MISOR_TUNE_MG_TAIL:
+        if (value != 0 && value != 1) return fail(MISOR_EINVAL, "MG_TAIL is 0 or 1");
+        g->mg_tail = value != 0;
+        return MISOR_OK;
     default: return fail(MISOR_EINVAL, "unknown tuning key %d", key);
     }
 }
@@ -840,6 +844,7 @@ int misor_get_tuning(const misor_grid* g, int key, int* value) {
     case MISOR_TUNE_LEX_TILE_W: *value = g->lex_tw ? g->lex_tw : kLexTileW; return MISOR_OK;
     case MISOR_TUNE_LEX_TILE_H: *value = g->lex_th ? g->lex_th : kLexTileH; return MISOR_OK;
     case MISOR_TUNE_LEX_WGS: *value = g->lex_wgs; return MISOR_OK;
+    case MISOR_TUNE_MG_TAIL: *value = g->mg_tail; return MISOR_OK;
     case MISOR_TUNE_NS_FUSE: *value = g->ns_fuse; return MISOR_OK;
     case MISOR_TUNE_FINISH2: *value = g->finish2; return MISOR_OK;
     case MISOR_TUNE_TB_RESERVE: *value = g->tb_reserve; return MISOR_OK;

@@ -229,6 +229,7 @@ struct misor_grid {
     // multigrid (misor_mg.hip): the level hierarchy below this grid, built by
     // the first misor_solve_mg
     struct MgHierarchy* mg = nullptr;
+    bool mg_tail = true;  // MISOR_TUNE_MG_TAIL: the LDS-resident levels cycled in one launch
 
     // stats
     bool timing = false;

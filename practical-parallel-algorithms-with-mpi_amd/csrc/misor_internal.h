@@ -330,6 +330,38 @@ void launch_mg_residual_restrict(hipStream_t s, const double* p, const double* r
 void launch_mg_prolong_correct(hipStream_t s, double* p, const double* e, int nic, int njc,
                                long long pitch, long long pitch_c);
 
+// The tail of a hierarchy -- its trailing levels that each fit the LDS of one
+// workgroup (small_solve_fits) -- cycled in ONE launch of one workgroup
+// (mg_tail.hip).  One entry per tail level, finest first:
+struct MgTailLevel {
+    double* p;          // the level's current pressure buffer (levels below the first: e)
+    double* rhs;        // its rhs (levels below the first: rc, written by the kernel)
+    int ni, nj;
+    long long pitch;
+    double idx2, idy2, cells;
+    double coef_smooth, coef_coarse;  // sor_consts(...).coef for omega_smooth / omega_coarse
+};
+// ... and the launch's state.  The kernel reads the first group and writes the
+// second.  It runs cycles while res >= epssq and fewer than maxcycles are done,
+// from cycles0 done with residual res0 (a tail below level 0 runs one cycle:
+// cycles0 0, res0 1, epssq 0, maxcycles 1).
+struct MgTailState {
+    int nu1, nu2, maxcycles, cycles0, itermax_coarse;
+    double epssq, res0;
+    double epssq_coarse, nband_coarse;  // the coarsest solve's eps^2 and its near band (< 0: none)
+    int cycles;       // cycles completed
+    int near;         // 1: stopped inside cycle `cycles` + 1, before an iteration of its
+                      // coarsest solve whose res fell within nband_coarse of epssq_coarse: the
+                      // down half of that cycle is done (every level's p and rhs stored), the
+                      // coarsest e is zero; the host finishes the cycle (misor_mg.hip)
+    double res;       // the first tail level's residual after the last completed cycle
+    double res_part;  // ... and as far as the cycle stopped in got (its pre-smoothing)
+};
+size_t mg_tail_lds(int ni, int nj);  // of a tail whose first level is ni x nj
+hipError_t mg_tail_prepare();        // once per device before the first launch
+void launch_mg_tail(hipStream_t s, const MgTailLevel* levels, int count, MgTailState* st,
+                    size_t lds);
+
 // 8-neighbour halo exchange of one field (halo.hip): regions in local cell
 // coordinates; direction order L, R, B, T, BL, BR, TL, TR
 constexpr int kDirs = 8;

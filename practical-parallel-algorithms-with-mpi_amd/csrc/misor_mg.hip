@@ -11,6 +11,13 @@
 // or the whole-solve LDS kernel.  The only kernels of its own are the two
 // transfers of mg_kernels.hip; they add no host round trip to a cycle.
 //
+// The tail of the hierarchy -- its trailing levels that each fit the LDS of a
+// workgroup -- is cycled by ONE launch of mg_tail.hip's kernel instead, when it
+// has two levels or more (MISOR_TUNE_MG_TAIL): cycle() hands the cycle to
+// tail_run at the tail's first level, and where that is level 0 the loop over
+// the cycles runs in the kernel too.  The bits are those of the level-by-level
+// path.
+//
 // Every argument check precedes the first HIP call.
 
 #include "misor_grid.h"
@@ -24,6 +31,17 @@ struct MgHierarchy {
     std::vector<hipEvent_t> ev;
     std::vector<int> kind;
     size_t ev_used = 0;
+    // the tail (misor_mg_tail): levels lv[tail_first ..], tail_count of them;
+    // their descriptors and the launch's state on the device with a pinned host
+    // mirror, and what the device holds of both (tail_up: the input fields)
+    int tail_first = 0, tail_count = 0;
+    MgTailLevel* tail_lv = nullptr;
+    MgTailLevel* tail_lv_host = nullptr;
+    MgTailState* tail_st = nullptr;
+    MgTailState* tail_st_host = nullptr;
+    std::vector<MgTailLevel> tail_lv_up;
+    MgTailState tail_up{};
+    bool tail_st_valid = false;
 };
 
 namespace {
@@ -98,6 +116,50 @@ int smooth(misor_grid* g, double omega, int nu, double* res) {
 void free_levels(MgHierarchy* h) {
     for (size_t l = 1; l < h->lv.size(); ++l) misor_destroy(h->lv[l]);
     h->lv.clear();
+    (void)hipFree(h->tail_lv);
+    (void)hipFree(h->tail_st);
+    (void)hipHostFree(h->tail_lv_host);
+    (void)hipHostFree(h->tail_st_host);
+    h->tail_lv = h->tail_lv_host = nullptr;
+    h->tail_st = h->tail_st_host = nullptr;
+    h->tail_lv_up.clear();
+    h->tail_st_valid = false;
+    h->tail_first = h->tail_count = 0;
+}
+
+// first index and length of the maximal run of trailing levels that fit the
+// one-workgroup LDS kernel (n levels, shape(l, &ni, &nj)); none: first = n
+template <class Shape>
+void tail_rule(int n, Shape shape, int* first, int* count) {
+    int f = n;
+    for (int l = n - 1; l >= 0; --l) {
+        int ni = 0, nj = 0;
+        shape(l, &ni, &nj);
+        if (!small_solve_fits(ni, nj)) break;
+        f = l;
+    }
+    *first = f;
+    *count = n - f;
+}
+
+// the tail's device blocks (a tail of one level is the coarsest solve alone
+// and stays on the level-by-level path: nothing to allocate)
+int ensure_tail(misor_grid* g) {
+    MgHierarchy* h = g->mg;
+    tail_rule((int)h->lv.size(),
+              [&](int l, int* ni, int* nj) {
+                  *ni = h->lv[l]->desc.imax;
+                  *nj = h->lv[l]->desc.jmax;
+              },
+              &h->tail_first, &h->tail_count);
+    if (h->tail_count < 2) return MISOR_OK;
+    const size_t bytes = (size_t)h->tail_count * sizeof(MgTailLevel);
+    HIPCHK(hipMalloc(&h->tail_lv, bytes));
+    HIPCHK(hipMalloc(&h->tail_st, sizeof(MgTailState)));
+    HIPCHK(hipHostMalloc(&h->tail_lv_host, bytes));
+    HIPCHK(hipHostMalloc(&h->tail_st_host, sizeof(MgTailState)));
+    HIPCHK(mg_tail_prepare());
+    return MISOR_OK;
 }
 
 // (re)build the levels below g for coarse_cells.  A new level comes with a
@@ -132,9 +194,19 @@ int ensure_hierarchy(misor_grid* g, int coarse_cells) {
             }
             h->lv.push_back(c);
         }
+        const int rc = ensure_tail(g);
+        if (rc) {
+            free_levels(h);
+            return rc;
+        }
     }
-    for (size_t l = 1; l < h->lv.size(); ++l)
+    for (size_t l = 1; l < h->lv.size(); ++l) {
         if (h->lv[l]->stream != g->stream) MISOR_TRY(misor_set_stream(h->lv[l], g->stream));
+        // the levels' solves test their loops as the grid's own do
+        // (MISOR_TUNE_NEAR_BAND), on either path
+        h->lv[l]->near_rel = g->near_rel;
+        h->lv[l]->near_exp = g->near_exp;
+    }
     return MISOR_OK;
 }
 
@@ -146,15 +218,19 @@ int collect_transfer_times(misor_grid* g) {
     for (size_t k = 0; k < h->ev_used; ++k) {
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, h->ev[2 * k], h->ev[2 * k + 1]));
-        g->stats.mg_transfer_ms[h->kind[k]] += ms;
+        if (h->kind[k] == 2) {
+            g->stats.mg_tail_ms += ms;
+        } else {
+            g->stats.mg_transfer_ms[h->kind[k]] += ms;
+            g->stats.mg_transfers += 1;
+        }
     }
-    g->stats.mg_transfers += (long long)h->ev_used;
     h->ev_used = 0;
     return MISOR_OK;
 }
 
-// the start (kind 0 / 1) or stop (kind < 0) event of the next pair around a
-// timed transfer launch, recorded on the stream.  A pair counts once its stop
+// the start (kind 0 / 1; 2: a tail launch) or stop (kind < 0) event of the next
+// pair around a timed launch, recorded on the stream.  A pair counts once its stop
 // is recorded: a start whose stop never came (an error in between) is reused.
 int record_transfer(misor_grid* g, int kind) {
     MgHierarchy* h = g->mg;
@@ -172,15 +248,12 @@ int record_transfer(misor_grid* g, int kind) {
     return MISOR_OK;
 }
 
-// One cycle on level l; *res: solveRB's residual of the level's last smoothing
-// iteration (the coarsest level: of its solve), untouched if none ran.
-int cycle(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
+// The downward half of a cycle on level l (not the coarsest): pre-smoothing,
+// rc into the next level's rhs, e = 0 there.  *res: solveRB's residual of the
+// last smoothing iteration, untouched if none ran.
+int cycle_down(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
     MgHierarchy* h = g0->mg;
     misor_grid* f = h->lv[l];
-    if (l + 1 == h->lv.size()) {
-        int it = 0;
-        return solve_with(f, q.omega_coarse, q.eps_coarse, q.itermax_coarse, &it, res);
-    }
     misor_grid* c = h->lv[l + 1];
     const bool timed = l == 0 && g0->timing;
     MISOR_TRY(smooth(f, q.omega_smooth, q.nu1, res));
@@ -197,14 +270,124 @@ int cycle(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
                             (size_t)c->pitch * sizeof(double), 0,
                             (size_t)(c->loc.ni + 2) * sizeof(double), (size_t)c->loc.nj + 2,
                             g0->stream));
-    double rc_unused = 0.0;
-    MISOR_TRY(cycle(g0, q, l + 1, &rc_unused));
+    return MISOR_OK;
+}
+
+// ... and the upward half: the correction from the next level, post-smoothing
+int cycle_up(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
+    MgHierarchy* h = g0->mg;
+    misor_grid* f = h->lv[l];
+    misor_grid* c = h->lv[l + 1];
+    const bool timed = l == 0 && g0->timing;
     if (timed) MISOR_TRY(record_transfer(g0, 1));
     launch_mg_prolong_correct(g0->stream, pbuf(f, f->cur), pbuf(c, c->cur), c->loc.ni, c->loc.nj,
                               f->pitch, c->pitch);
     HIPCHK(hipGetLastError());
     if (timed) MISOR_TRY(record_transfer(g0, -1));
     return smooth(f, q.omega_smooth, q.nu2, res);
+}
+
+bool tail_fused(const misor_grid* g0) { return g0->mg_tail && g0->mg->tail_count >= 2; }
+
+// The tail's cycles in one launch.  *n cycles are done with residual *res (of
+// the tail's first level); below level 0 the launch runs one cycle, at level 0
+// misor_solve_mg's loop to eps^2 = epssq and maxcycles.  Where the coarsest
+// solve came near its threshold the kernel has stopped inside a cycle, its
+// downward half done and e zero on the coarsest level: that cycle is finished
+// level by level here -- the coarsest solve (with its exact tail) and the
+// upward halves -- and counted; the caller's loop goes on from there.
+int tail_run(misor_grid* g0, const misor_mg_params& q, double epssq, int maxcycles, int* n,
+             double* res) {
+    MgHierarchy* h = g0->mg;
+    const size_t first = (size_t)h->tail_first, count = (size_t)h->tail_count;
+    // the descriptors: the current buffers and the coefficients of this call,
+    // the same bits as solve_with gives the level's solve
+    std::vector<MgTailLevel> lv(count);
+    for (size_t k = 0; k < count; ++k) {
+        misor_grid* f = h->lv[first + k];
+        MgTailLevel& d = lv[k];
+        memset(&d, 0, sizeof d);
+        d.p = pbuf(f, f->cur);
+        d.rhs = f->fld[kRhs];
+        d.ni = f->loc.ni;
+        d.nj = f->loc.nj;
+        d.pitch = f->pitch;
+        d.idx2 = f->sp.idx2;
+        d.idy2 = f->sp.idy2;
+        d.cells = (double)f->desc.imax * (double)f->desc.jmax;
+        d.coef_smooth = sor_consts(f->desc.dx, f->desc.dy, q.omega_smooth, f->desc.variant).coef;
+        d.coef_coarse = sor_consts(f->desc.dx, f->desc.dy, q.omega_coarse, f->desc.variant).coef;
+    }
+    if (h->tail_lv_up.size() != count ||
+        memcmp(h->tail_lv_up.data(), lv.data(), count * sizeof(MgTailLevel)) != 0) {
+        memcpy(h->tail_lv_host, lv.data(), count * sizeof(MgTailLevel));
+        HIPCHK(hipMemcpyAsync(h->tail_lv, h->tail_lv_host, count * sizeof(MgTailLevel),
+                              hipMemcpyHostToDevice, g0->stream));
+        h->tail_lv_up = lv;
+    }
+    MgTailState s;
+    memset(&s, 0, sizeof s);
+    s.nu1 = q.nu1;
+    s.nu2 = q.nu2;
+    s.maxcycles = maxcycles;
+    s.cycles0 = *n;
+    s.itermax_coarse = q.itermax_coarse;
+    s.epssq = epssq;
+    s.res0 = *res;
+    s.epssq_coarse = q.eps_coarse * q.eps_coarse;
+    s.nband_coarse = near_band_abs(h->lv.back()->near_rel, s.epssq_coarse);
+    if (!h->tail_st_valid || memcmp(&h->tail_up, &s, sizeof s) != 0) {
+        *h->tail_st_host = s;
+        HIPCHK(hipMemcpyAsync(h->tail_st, h->tail_st_host, sizeof s, hipMemcpyHostToDevice,
+                              g0->stream));
+        memcpy(&h->tail_up, &s, sizeof s);
+        h->tail_st_valid = true;
+    }
+    if (g0->timing) MISOR_TRY(record_transfer(g0, 2));
+    launch_mg_tail(g0->stream, h->tail_lv, (int)count, h->tail_st,
+                   mg_tail_lds(lv[0].ni, lv[0].nj));
+    HIPCHK(hipGetLastError());
+    if (g0->timing) MISOR_TRY(record_transfer(g0, -1));
+    HIPCHK(hipMemcpyAsync(h->tail_st_host, h->tail_st, sizeof s, hipMemcpyDeviceToHost,
+                          g0->stream));
+    MISOR_TRY(wait_stream(g0, g0->stream));
+    const MgTailState out = *h->tail_st_host;
+    g0->stats.mg_tail_levels = (int)count;
+    g0->stats.mg_tail_launches += 1;
+    *n = out.cycles;
+    *res = out.res;
+    if (!out.near) return MISOR_OK;
+    double r = out.res_part, unused = 0.0;
+    int it = 0;
+    MISOR_TRY(solve_with(h->lv.back(), q.omega_coarse, q.eps_coarse, q.itermax_coarse, &it,
+                         &unused));
+    for (size_t l = h->lv.size() - 1; l-- > first;)
+        MISOR_TRY(cycle_up(g0, q, l, l == first ? &r : &unused));
+    g0->stats.mg_tail_fallbacks += 1;
+    *n = out.cycles + 1;
+    *res = r;
+    return MISOR_OK;
+}
+
+// One cycle on level l; *res: solveRB's residual of the level's last smoothing
+// iteration (the coarsest level: of its solve), untouched if none ran.
+int cycle(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
+    MgHierarchy* h = g0->mg;
+    if (tail_fused(g0) && l == (size_t)h->tail_first) {
+        int n = 0;
+        double r = 1.0;  // one cycle: 1 >= 0 and 0 < 1
+        MISOR_TRY(tail_run(g0, q, 0.0, 1, &n, &r));
+        *res = r;
+        return MISOR_OK;
+    }
+    if (l + 1 == h->lv.size()) {
+        int it = 0;
+        return solve_with(h->lv[l], q.omega_coarse, q.eps_coarse, q.itermax_coarse, &it, res);
+    }
+    MISOR_TRY(cycle_down(g0, q, l, res));
+    double rc_unused = 0.0;
+    MISOR_TRY(cycle(g0, q, l + 1, &rc_unused));
+    return cycle_up(g0, q, l, res);
 }
 
 }  // namespace
@@ -251,6 +434,19 @@ int misor_mg_levels(int imax, int jmax, int coarse_cells, int* nlevels, int* sha
     return MISOR_OK;
 }
 
+int misor_mg_tail(int imax, int jmax, int coarse_cells, int* first, int* count) {
+    if (!first || !count) return fail(MISOR_EINVAL, "misor_mg_tail: null first or count");
+    int shapes[2 * 64], n = 0;  // a side halves per level: far fewer than 64 levels
+    MISOR_TRY(misor_mg_levels(imax, jmax, coarse_cells, &n, shapes, 64));
+    tail_rule(n,
+              [&](int l, int* ni, int* nj) {
+                  *ni = shapes[2 * l];
+                  *nj = shapes[2 * l + 1];
+              },
+              first, count);
+    return MISOR_OK;
+}
+
 int misor_solve_mg(misor_grid* g, const misor_mg_params* prm, int* cycles, double* res) {
     if (prm) MISOR_TRY(check_params(*prm));
     if (!g) return fail(MISOR_EINVAL, "misor_solve_mg: null grid");
@@ -265,10 +461,18 @@ int misor_solve_mg(misor_grid* g, const misor_mg_params* prm, int* cycles, doubl
     int n = 0;
     double r = 1.0;  // as solveRB's loop (solver.c:196)
     int rc = MISOR_OK;
-    while ((r >= epssq) && (n < q.maxcycles)) {
-        rc = cycle(g, q, 0, &r);
-        if (rc) break;
-        ++n;
+    g->stats.mg_tail_levels = 0;
+    if (tail_fused(g) && g->mg->tail_first == 0) {
+        // the grid itself fits: the loop runs in the kernel, which comes back
+        // before the end only where the host had a cycle to finish
+        while (!rc && (r >= epssq) && (n < q.maxcycles))
+            rc = tail_run(g, q, epssq, q.maxcycles, &n, &r);
+    } else {
+        while ((r >= epssq) && (n < q.maxcycles)) {
+            rc = cycle(g, q, 0, &r);
+            if (rc) break;
+            ++n;
+        }
     }
     g->stats.mg_cycles = n;
     g->stats.mg_levels = (int)g->mg->lv.size();

@@ -28,7 +28,7 @@ LEX_A4, LEX_SEQ = 0, 1
  TUNE_TSTEPS, TUNE_TB_VARIANT, TUNE_TB_ROWS, TUNE_TB_PERSISTENT, TUNE_NS_FUSE,
  TUNE_FINISH2, TUNE_TB_RESERVE, TUNE_TB_CHAIN, TUNE_NEAR_BAND, TUNE_RES_LITE,
  TUNE_EDGE_STEAL, TUNE_LEX_TILED, TUNE_LEX_TILE_W, TUNE_LEX_TILE_H,
- TUNE_LEX_WGS) = range(1, 21)
+ TUNE_LEX_WGS, TUNE_MG_TAIL) = range(1, 22)
 COMM_ID_BYTES = 128
 # 3D field ids (misor3_*)
 P3, RHS3, U3, V3, W3, F3, G3, H3 = range(8)
@@ -73,6 +73,14 @@ class Stats(C.Structure):
                 ("lite_misses", C.c_longlong),
                 ("mg_cycles", C.c_int), ("mg_levels", C.c_int),
                 ("mg_transfer_ms", C.c_double * 2), ("mg_transfers", C.c_longlong)]
+
+
+class StatsTail(Stats):
+    """misor_stats whole: Stats is its layout up to mg_transfers, kept under that
+    name with those fields last; what was appended since follows here (a ctypes
+    subclass lays its fields out behind the base's, as C does)"""
+    _fields_ = [("mg_tail_levels", C.c_int), ("mg_tail_launches", C.c_longlong),
+                ("mg_tail_fallbacks", C.c_longlong), ("mg_tail_ms", C.c_double)]
 
 
 class MgInfo3(C.Structure):
@@ -129,6 +137,8 @@ SIGNATURES = {
     "misor_solve_rb_n": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]),
     "misor_solve_lex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]),
     "misor_mg_default_params": (C.c_int, [C.c_void_p, C.POINTER(MgParams)]),
+    "misor_mg_tail": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                C.POINTER(C.c_int)]),
     "misor_mg_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.c_int]),
     "misor_solve_mg": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.POINTER(C.c_int), _dp]),
@@ -145,7 +155,7 @@ SIGNATURES = {
     "misor_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "misor_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "misor_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
-    "misor_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
+    "misor_get_stats": (C.c_int, [C.c_void_p, C.POINTER(StatsTail)]),
     "misor_reset_stats": (C.c_int, [C.c_void_p]),
     "misor_chain_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong,
                                     C.POINTER(C.c_longlong)]),
@@ -249,6 +259,15 @@ def mg_levels(imax, jmax, coarse_cells=64):
     shapes = (C.c_int * (2 * n.value))()
     _check(lib().misor_mg_levels(imax, jmax, coarse_cells, C.byref(n), shapes, n.value))
     return [(shapes[2 * k], shapes[2 * k + 1]) for k in range(n.value)]
+
+
+def mg_tail(imax, jmax, coarse_cells=64):
+    """(first, count) of the tail of mg_levels(imax, jmax, coarse_cells): its trailing
+    levels that each fit the LDS of one workgroup; count 0 (first = the number of
+    levels): none does (misor_mg_tail; host-only)"""
+    first, count = C.c_int(0), C.c_int(0)
+    _check(lib().misor_mg_tail(imax, jmax, coarse_cells, C.byref(first), C.byref(count)))
+    return first.value, count.value
 
 
 def mg3_levels(imax, jmax, kmax, coarse_cells=512):
@@ -426,7 +445,7 @@ class Grid:
         _check(lib().misor_enable_timing(self.h, 1 if on else 0))
 
     def stats(self):
-        s = Stats()
+        s = StatsTail()
         _check(lib().misor_get_stats(self.h, C.byref(s)))
         return {"sweeps": s.sweeps, "launches": s.launches, "sweep_ms": s.sweep_ms,
                 "timed_sweeps": s.timed_sweeps, "timed_passes": s.timed_passes,
@@ -436,7 +455,9 @@ class Grid:
                 "chained": s.chained, "ns_ms": list(s.ns_ms), "ns_calls": list(s.ns_calls),
                 "lite_misses": s.lite_misses, "mg_cycles": s.mg_cycles,
                 "mg_levels": s.mg_levels, "mg_transfer_ms": list(s.mg_transfer_ms),
-                "mg_transfers": s.mg_transfers}
+                "mg_transfers": s.mg_transfers, "mg_tail_levels": s.mg_tail_levels,
+                "mg_tail_launches": s.mg_tail_launches,
+                "mg_tail_fallbacks": s.mg_tail_fallbacks, "mg_tail_ms": s.mg_tail_ms}
 
     def reset_stats(self):
         _check(lib().misor_reset_stats(self.h))
