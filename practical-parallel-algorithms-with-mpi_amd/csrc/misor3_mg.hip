@@ -45,20 +45,20 @@ bool mg3_coarsen(const int n[3], int coarse_cells, int nc[3]) {
 
 int check_params(const misor_mg_params& q) {
     if (q.nu1 < 0 || q.nu2 < 0)
-        return fail3(MISOR_EINVAL, "misor3_solve_mg: nu1 = %d, nu2 = %d: counts must be >= 0",
-                     q.nu1, q.nu2);
+        return fail(MISOR_EINVAL, "misor3_solve_mg: nu1 = %d, nu2 = %d: counts must be >= 0",
+                    q.nu1, q.nu2);
     if (q.nu1 + q.nu2 < 1)
-        return fail3(MISOR_EINVAL, "misor3_solve_mg: nu1 + nu2 must be >= 1 (a cycle smooths)");
+        return fail(MISOR_EINVAL, "misor3_solve_mg: nu1 + nu2 must be >= 1 (a cycle smooths)");
     if (!(q.omega_smooth > 0.0) || !(q.omega_coarse > 0.0))
-        return fail3(MISOR_EINVAL, "misor3_solve_mg: omega_smooth and omega_coarse must be > 0");
+        return fail(MISOR_EINVAL, "misor3_solve_mg: omega_smooth and omega_coarse must be > 0");
     if (q.coarse_cells < 0)
-        return fail3(MISOR_EINVAL, "misor3_solve_mg: coarse_cells = %d must be >= 0",
-                     q.coarse_cells);
+        return fail(MISOR_EINVAL, "misor3_solve_mg: coarse_cells = %d must be >= 0",
+                    q.coarse_cells);
     if (q.itermax_coarse < 0)
-        return fail3(MISOR_EINVAL, "misor3_solve_mg: itermax_coarse = %d must be >= 0",
-                     q.itermax_coarse);
+        return fail(MISOR_EINVAL, "misor3_solve_mg: itermax_coarse = %d must be >= 0",
+                    q.itermax_coarse);
     if (q.maxcycles < 0)
-        return fail3(MISOR_EINVAL, "misor3_solve_mg: maxcycles = %d must be >= 0", q.maxcycles);
+        return fail(MISOR_EINVAL, "misor3_solve_mg: maxcycles = %d must be >= 0", q.maxcycles);
     return MISOR_OK;
 }
 
@@ -95,7 +95,7 @@ int ensure_hierarchy(misor_grid3* g, int coarse_cells) {
     if (!g->mg) g->mg = new Mg3Hierarchy();
     Mg3Hierarchy* h = g->mg;
     if (h->coarse_cells == coarse_cells && !h->lv.empty()) return MISOR_OK;
-    HIPCHK3(hipStreamSynchronize(g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
     free_levels(h);
     h->coarse_cells = coarse_cells;
     h->lv.push_back(g);
@@ -125,10 +125,10 @@ int ensure_hierarchy(misor_grid3* g, int coarse_cells) {
 int collect_transfer_times(misor_grid3* g) {
     Mg3Hierarchy* h = g->mg;
     if (!h->ev_used) return MISOR_OK;
-    HIPCHK3(hipStreamSynchronize(g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
     for (size_t k = 0; k < h->ev_used; ++k) {
         float ms = 0.f;
-        HIPCHK3(hipEventElapsedTime(&ms, h->ev[2 * k], h->ev[2 * k + 1]));
+        HIPCHK(hipEventElapsedTime(&ms, h->ev[2 * k], h->ev[2 * k + 1]));
         g->mg_info.transfer_ms[h->kind[k]] += ms;
     }
     g->mg_info.transfers += (long long)h->ev_used;
@@ -143,14 +143,14 @@ int record_transfer(misor_grid3* g, int kind) {
     Mg3Hierarchy* h = g->mg;
     while (h->ev.size() < 2 * kMg3EventPairs) {
         hipEvent_t e;
-        HIPCHK3(hipEventCreate(&e));
+        HIPCHK(hipEventCreate(&e));
         h->ev.push_back(e);
     }
     h->kind.resize(kMg3EventPairs);
     const bool stop = kind < 0;
-    if (!stop && h->ev_used == kMg3EventPairs) MISOR3_TRY(collect_transfer_times(g));
+    if (!stop && h->ev_used == kMg3EventPairs) MISOR_TRY(collect_transfer_times(g));
     if (!stop) h->kind[h->ev_used] = kind;
-    HIPCHK3(hipEventRecord(h->ev[2 * h->ev_used + (stop ? 1 : 0)], g->stream));
+    HIPCHK(hipEventRecord(h->ev[2 * h->ev_used + (stop ? 1 : 0)], g->stream));
     if (stop) ++h->ev_used;
     return MISOR_OK;
 }
@@ -168,25 +168,25 @@ int cycle(misor_grid3* g0, const misor_mg_params& q, size_t l, double* res) {
     }
     misor_grid3* c = h->lv[l + 1];
     const bool timed = l == 0 && g0->timing;
-    MISOR3_TRY(smooth(f, q.omega_smooth, q.nu1, res));
+    MISOR_TRY(smooth(f, q.omega_smooth, q.nu1, res));
     // rc = R (rhs - lap p) into the coarse rhs
     const double dx2 = f->dx * f->dx, dy2 = f->dy * f->dy, dz2 = f->dz * f->dz;
-    if (timed) MISOR3_TRY(record_transfer(g0, 0));
+    if (timed) MISOR_TRY(record_transfer(g0, 0));
     launch_mg3_residual_restrict(g0->stream, f->g, c->g, f->fld[MISOR3_P], f->fld[MISOR3_RHS],
                                  c->fld[MISOR3_RHS], 1.0 / dx2, 1.0 / dy2, 1.0 / dz2);
-    HIPCHK3(hipGetLastError());
-    if (timed) MISOR3_TRY(record_transfer(g0, -1));
+    HIPCHK(hipGetLastError());
+    if (timed) MISOR_TRY(record_transfer(g0, -1));
     // e = 0 over the whole allocation, ghosts, edges and corners included; the
     // partner buffer is a copy of it before the first sweep that uses it
     launch_fill(g0->stream, c->mem[MISOR3_P], c->nalloc, 0.0);
-    HIPCHK3(hipGetLastError());
+    HIPCHK(hipGetLastError());
     c->alt_stale = true;
     double rc_unused = 0.0;
-    MISOR3_TRY(cycle(g0, q, l + 1, &rc_unused));
-    if (timed) MISOR3_TRY(record_transfer(g0, 1));
+    MISOR_TRY(cycle(g0, q, l + 1, &rc_unused));
+    if (timed) MISOR_TRY(record_transfer(g0, 1));
     launch_mg3_prolong_correct(g0->stream, f->g, c->g, f->fld[MISOR3_P], c->fld[MISOR3_P]);
-    HIPCHK3(hipGetLastError());
-    if (timed) MISOR3_TRY(record_transfer(g0, -1));
+    HIPCHK(hipGetLastError());
+    if (timed) MISOR_TRY(record_transfer(g0, -1));
     f->alt_stale = true;  // p changed outside a sweep
     return smooth(f, q.omega_smooth, q.nu2, res);
 }
@@ -204,18 +204,18 @@ void mg3_free(misor_grid3* g) {
 extern "C" {
 
 int misor3_mg_default_params(const misor_grid3* g, misor_mg_params* out) {
-    if (!g || !out) return fail3(MISOR_EINVAL, "misor3_mg_default_params: null argument");
+    if (!g || !out) return fail(MISOR_EINVAL, "misor3_mg_default_params: null argument");
     *out = default_params(g);
     return MISOR_OK;
 }
 
 int misor3_mg_levels(int imax, int jmax, int kmax, int coarse_cells, int* nlevels, int* shapes,
                      int cap) {
-    if (!nlevels) return fail3(MISOR_EINVAL, "misor3_mg_levels: null nlevels");
+    if (!nlevels) return fail(MISOR_EINVAL, "misor3_mg_levels: null nlevels");
     if (imax < 2 || jmax < 2 || kmax < 2)
-        return fail3(MISOR_EINVAL, "misor3_mg_levels: imax, jmax, kmax must be >= 2");
+        return fail(MISOR_EINVAL, "misor3_mg_levels: imax, jmax, kmax must be >= 2");
     if (coarse_cells < 0 || cap < 0 || (cap > 0 && !shapes))
-        return fail3(MISOR_EINVAL, "misor3_mg_levels: coarse_cells, cap >= 0; shapes for cap > 0");
+        return fail(MISOR_EINVAL, "misor3_mg_levels: coarse_cells, cap >= 0; shapes for cap > 0");
     int cnt = 0, n[3] = {imax, jmax, kmax};
     for (;;) {
         if (cnt < cap)
@@ -230,14 +230,14 @@ int misor3_mg_levels(int imax, int jmax, int kmax, int coarse_cells, int* nlevel
 }
 
 int misor3_solve_mg(misor_grid3* g, const misor_mg_params* prm, int* cycles, double* res) {
-    if (prm) MISOR3_TRY(check_params(*prm));
-    if (!g) return fail3(MISOR_EINVAL, "misor3_solve_mg: null grid");
+    if (prm) MISOR_TRY(check_params(*prm));
+    if (!g) return fail(MISOR_EINVAL, "misor3_solve_mg: null grid");
     if (g->nranks > 1)
-        return fail3(MISOR_ESTATE,
-                     "misor3_solve_mg has no decomposed form yet (single rank only)");
+        return fail(MISOR_ESTATE,
+                    "misor3_solve_mg has no decomposed form yet (single rank only)");
     const misor_mg_params q = prm ? *prm : default_params(g);
-    HIPCHK3(hipSetDevice(g->device));
-    MISOR3_TRY(ensure_hierarchy(g, q.coarse_cells));
+    HIPCHK(hipSetDevice(g->device));
+    MISOR_TRY(ensure_hierarchy(g, q.coarse_cells));
     const double epssq = g->desc.eps * g->desc.eps;
     int n = 0;
     double r = 1.0;  // as the solve's loop (solver.c:196)
@@ -250,14 +250,14 @@ int misor3_solve_mg(misor_grid3* g, const misor_mg_params* prm, int* cycles, dou
     g->mg_info.cycles = n;
     g->mg_info.levels = (int)g->mg->lv.size();
     if (rc) return rc;
-    MISOR3_TRY(collect_transfer_times(g));
+    MISOR_TRY(collect_transfer_times(g));
     if (cycles) *cycles = n;
     if (res) *res = r;
     return MISOR_OK;
 }
 
 int misor3_get_mg_info(const misor_grid3* g, misor3_mg_info* out) {
-    if (!g || !out) return fail3(MISOR_EINVAL, "misor3_get_mg_info: null argument");
+    if (!g || !out) return fail(MISOR_EINVAL, "misor3_get_mg_info: null argument");
     *out = g->mg_info;
     return MISOR_OK;
 }

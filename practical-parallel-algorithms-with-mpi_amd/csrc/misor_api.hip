@@ -5,6 +5,7 @@
 // misor_ns.hip, communication in misor_comm.hip, launch plans in
 // misor_plan.hip; their shared state is struct misor_grid (misor_grid.h).
 
+#include "decomp3.h"  // size_of_rank
 #include "misor_grid.h"
 
 namespace {
@@ -19,13 +20,6 @@ void dims_create(int n, int dims[2]) {
     dims[0] = n / best;
     dims[1] = best;
 }
-
-// sizeOfRank (assignment-5/skeleton/src/solver.c:30-32)
-int size_of_rank(int rank, int size, int n) { return n / size + ((n % size > rank) ? 1 : 0); }
-
-std::mutex g_groups_mu;
-std::map<std::string, std::shared_ptr<LocalGroup>> g_groups;
-constexpr char kLocalPrefix[] = "LOCAL:";
 
 }  // namespace
 
@@ -347,25 +341,13 @@ int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
         const size_t hb = (size_t)maxtot * sizeof(double);
         if (hipMalloc(&g->sendbuf, hb) != hipSuccess || hipMalloc(&g->recvbuf, hb) != hipSuccess)
             CREATE_FAIL(MISOR_ENOMEM, "halo buffer allocation failed");
-        if (memcmp(d->comm_id, kLocalPrefix, sizeof kLocalPrefix - 1) == 0) {
-            char name[MISOR_COMM_ID_BYTES + 1];
-            memcpy(name, d->comm_id, MISOR_COMM_ID_BYTES);
-            name[MISOR_COMM_ID_BYTES] = '\0';
-            {
-                std::lock_guard<std::mutex> lk(g_groups_mu);
-                auto& G = g_groups[name];
-                if (!G) {
-                    G = std::make_shared<LocalGroup>();
-                    G->n = nranks;
-                    G->members.assign(nranks, nullptr);
-                    G->vals.assign(kMaxT * (size_t)nranks, 0.0);
-                }
-                if (G->n != nranks || G->members[d->rank])
-                    CREATE_FAIL(MISOR_EINVAL, "local group %s: bad rank/size", name);
-                G->members[d->rank] = g;
-                g->local = G;
-                if (++G->joined == nranks) g_groups.erase(name);  // name reusable
-            }
+        char name[MISOR_COMM_ID_BYTES + 1];
+        // (no host scratch: this all-reduce stages on the device, la_stage / la_gather)
+        const LocalJoin joined =
+            join_local_group(d->comm_id, nranks, d->rank, g, 0, g->local, name);
+        if (joined == LocalJoin::kBadMember)
+            CREATE_FAIL(MISOR_EINVAL, "local group %s: bad rank/size", name);
+        if (joined == LocalJoin::kJoined) {
             bool lok = hipMalloc(&g->la_stage, sizeof(double) * 2 * kMaxT) == hipSuccess &&
                        hipMalloc(&g->la_gather, sizeof(double) * 2 * kMaxT * (size_t)nranks) ==
                            hipSuccess;

@@ -137,7 +137,7 @@ int exchange(misor_grid* g, double* field, int d, hipStream_t s) {
         // recorded its pack event; barrier 2: every rank has recorded its copy
         // event (so the next exchange waits on this exchange's records).
         static const int opposite[kDirs] = {1, 0, 3, 2, 7, 6, 5, 4};
-        LocalGroup& G = *g->local;
+        LocalGroup<misor_grid>& G = *g->local;
         HIPCHK(hipStreamWaitEvent(s, g->lx_cp, 0));
         for (int k = 0; k < kDirs; ++k)
             if (g->nbr[k] >= 0) HIPCHK(hipStreamWaitEvent(s, G.members[g->nbr[k]]->lx_cp, 0));
@@ -199,7 +199,7 @@ int allreduce(misor_grid* g, double* dev, int n, int is_max, hipStream_t s) {
         // reused two all-reduces later once every rank has read it), gathers
         // every rank's staged values after barrier 1 and combines them in rank
         // order on its device; barrier 2 publishes the read events.
-        LocalGroup& G = *g->local;
+        LocalGroup<misor_grid>& G = *g->local;
         const int par = (int)(g->la_gen++ & 1);
         double* stage = g->la_stage + par * kMaxT;
         double* gather = g->la_gather + (size_t)par * G.n * kMaxT;

@@ -12,79 +12,18 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
-#include <condition_variable>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <thread>
 #include <vector>
 
-#include "misor_internal.h"
+#include "local_group.h"
+#include "misor_err.h"
 
 using namespace misor;
-
-// helpers shared by the units: not exported from libmisor.so
-#define MISOR_HIDDEN __attribute__((visibility("hidden")))
-
-// record an error message for misor_last_error and return code
-MISOR_HIDDEN int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define HIPCHK(x)                                                                         \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess)                                                             \
-            return fail(MISOR_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                        \
-    } while (0)
-
-// return the code of a failed call of the library's own (one that has
-// already recorded its message through fail)
-#define MISOR_TRY(x)           \
-    do {                       \
-        const int rc_ = (x);   \
-        if (rc_) return rc_;   \
-    } while (0)
-
-#define NCCLCHK(x)                                                                       \
-    do {                                                                                  \
-        ncclResult_t r_ = (x);                                                            \
-        if (r_ != ncclSuccess)                                                            \
-            return fail(MISOR_ECOMM, "%s: %s (%s:%d)", #x, ncclGetErrorString(r_),        \
-                        __FILE__, __LINE__);                                              \
-    } while (0)
 
 // kP2: third pressure buffer of decomposed runs (the pipelined pass loop of
 // misor_solve_rb_n writes pass k's result while pass k-1's source is kept)
 enum { kP0 = 0, kP1 = 1, kRhs = 2, kU = 3, kV = 4, kF = 5, kG = 6, kP2 = 7, kNumFields = 8 };
-
-// In-process transport: every rank of the group is a misor_grid owned by its
-// own host thread of ONE process (any devices, including all on one GPU).
-// Collectives are a host barrier plus device-to-device copies; the sum is
-// combined in rank order.  It exists so the decomposed kernels can be run and
-// checked on a single-GPU machine; across GPUs the RCCL path is used.
-struct LocalGroup {
-    int n = 0;
-    std::vector<misor_grid*> members;
-    std::vector<double> vals;  // n * kMaxT scratch for all-reduce
-    std::mutex m;
-    std::condition_variable cv;
-    int arrived = 0;
-    long long generation = 0;
-    int joined = 0, left = 0;
-
-    void barrier() {
-        std::unique_lock<std::mutex> lk(m);
-        const long long gen = generation;
-        if (++arrived == n) {
-            arrived = 0;
-            ++generation;
-            cv.notify_all();
-        } else {
-            cv.wait(lk, [&] { return generation != gen; });
-        }
-    }
-};
 
 struct misor_grid {
     int device = 0;
@@ -198,7 +137,7 @@ struct misor_grid {
     int nbr[kDirs] = {-1, -1, -1, -1, -1, -1, -1, -1};  // L R B T BL BR TL TR
     HaloPlan plan[2 * kMaxT + 2] = {};                   // by halo depth 1 .. 2*kMaxT + 1
     int max_depth = 2;                                   // deepest plan built
-    std::shared_ptr<LocalGroup> local;                   // in-process transport
+    std::shared_ptr<LocalGroup<misor_grid>> local;       // in-process transport (local_group.h)
     bool overlap = true;            // exchange on cstream while the interior sweeps
     hipStream_t cstream = nullptr;  // communication stream
     hipEvent_t ev_s = nullptr, ev_x = nullptr;

@@ -1,38 +1,23 @@
 // misor_grid3.h -- the state of a 3D grid (misor_grid3) and what the
-// translation units of the 3D path share (misor3d_api.hip, misor3_mg.hip).
+// host units of the 3D path share: misor3d_api.hip (lifecycle, transfers, the
+// Navier-Stokes step, tuning, timing), misor3_comm.hip (halo exchange,
+// all-reduce and gather over RCCL or the in-process transport),
+// misor3_solve.hip (misor3_solve, one function per schedule) and misor3_mg.hip
+// (multigrid).  The decomposition arithmetic is in decomp3.h.
 // Not part of the public ABI (include/misor.h).
 #pragma once
 
 #include <memory>
 
-#include "misor_internal.h"
+#include "decomp3.h"  // kHalo: halo planes per side in storage
+#include "local_group.h"
+#include "misor_err.h"
 
-#define MISOR3_HIDDEN __attribute__((visibility("hidden")))
-
-// sets the message misor_last_error() returns; returns code
-MISOR3_HIDDEN int fail3(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-
-#define HIPCHK3(x)                                                                         \
-    do {                                                                                   \
-        hipError_t e_ = (x);                                                               \
-        if (e_ != hipSuccess)                                                              \
-            return fail3(MISOR_EHIP, "%s: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                        \
-    } while (0)
-
-#define MISOR3_TRY(x)          \
-    do {                       \
-        const int rc_ = (x);   \
-        if (rc_) return rc_;   \
-    } while (0)
-
-constexpr int kHalo = 2;          // halo planes per side in storage
 constexpr int kSlack = 2;         // spare doubles before / after every buffer: the sweep's
                                   // 16-byte column-pair loads reach one past a row end
 constexpr int kBufs = 9;          // the 8 fields + the ping-pong partner of P
 constexpr int kAlt = 8;
 
-struct LocalGroup3;   // the in-process transport (misor3d_api.hip)
 struct Mg3Hierarchy;  // the multigrid levels below a grid (misor3_mg.hip)
 
 struct misor_grid3 {
@@ -74,7 +59,7 @@ struct misor_grid3 {
     // decomposition
     int nranks = 1, rank = 0, prev = -1, next = -1;
     ncclComm_t comm = nullptr;
-    std::shared_ptr<LocalGroup3> local;
+    std::shared_ptr<LocalGroup<misor_grid3>> local;  // in-process transport; vals: 4 per rank
     double* gstage = nullptr;     // rank 0: receive staging of misor3_gather (RCCL)
     // Cartesian process grid (misor3_create_cart)
     bool cart = false;
@@ -91,12 +76,44 @@ struct misor_grid3 {
 // misor3d_api.hip
 // a single-rank grid holding p, its partner and rhs only (no u, v, w, f, g,
 // h), on stream s: a multigrid level
-MISOR3_HIDDEN int create3_level(misor_grid3** out, const misor3_desc* d, hipStream_t s);
+MISOR_HIDDEN int create3_level(misor_grid3** out, const misor3_desc* d, hipStream_t s);
+
+inline bool dist(const misor_grid3* g) { return g->nranks > 1; }
+// plane kk of buffer b
+inline double* plane_ptr(misor_grid3* g, int b, int kk) {
+    return g->fld[b] + (long long)kk * g->g.sxy;
+}
+// what a rank contributes to the global array (decomp3.h own_span), as a box
+// of its local array
+inline misor::Box3 own_box(const misor3_local& L) {
+    const misor::Span3 x = misor::own_span(L, 0), y = misor::own_span(L, 1),
+                       z = misor::own_span(L, 2);
+    return {x.lo, y.lo, z.lo, x.count, y.count, z.count, L.n[0] + 2,
+            (long long)(L.n[0] + 2) * (L.n[1] + 2)};
+}
+
+// misor3_comm.hip: no-ops on a single rank
+// d-deep halo of buffer b of a slab grid: planes K-d+1..K to the next rank's
+// 1-d..0, planes 1..d to the previous rank's K+1..K+d
+MISOR_HIDDEN int exchange3(misor_grid3* g, int b, int d);
+// the 1-deep halo of buffer b of a Cartesian block on the axes of `axes` (bit
+// 0 x, 1 y, 2 z), in that order; an axis the process grid does not cut is
+// skipped by every rank alike
+MISOR_HIDDEN int exchange_cart(misor_grid3* g, int b, int axes);
+// all-reduce of n <= 4 device doubles (sum or max)
+MISOR_HIDDEN int allreduce3(misor_grid3* g, double* dev, int n, bool is_max);
+// misor3_gather of a decomposed grid: slabs / Cartesian blocks
+MISOR_HIDDEN int gather_slabs(misor_grid3* g, int field, double* host_global);
+MISOR_HIDDEN int gather_cart(misor_grid3* g, int field, double* host_global);
+
+// misor3_solve.hip
+// planes a workgroup of the fused sweep marches (MISOR3_TUNE_KCHUNK = 0)
+MISOR_HIDDEN int auto_kchunk(const misor::G3& g, int rows);
 // misor3_solve with omega, eps, itermax and the starting residual carry
 // res_seed in place of desc.omega, desc.eps, desc.itermax and 1.0; they and
 // the batch-size hint are put back, so the grid's next solve is unaffected
-MISOR3_HIDDEN int solve3_with(misor_grid3* g, double omega, double eps, int itermax,
-                              double res_seed, int* iters, double* res);
+MISOR_HIDDEN int solve3_with(misor_grid3* g, double omega, double eps, int itermax,
+                             double res_seed, int* iters, double* res);
 
 // misor3_mg.hip
-MISOR3_HIDDEN void mg3_free(misor_grid3* g);
+MISOR_HIDDEN void mg3_free(misor_grid3* g);

@@ -173,6 +173,37 @@ def test_solve_fixed_iterations_partition_independent(golden, box, itermax, dims
         assert np.array_equal(run_ranks(world, slab_rank)[0], out[0][2])
 
 
+def test_solve_epilogue_counts_on_2x1x1(golden):
+    """what the Cartesian schedule does after its loop (test_ns3d_gpu.py's
+    test_solve_epilogue_counts_every_schedule_alike, same box and solves): two
+    timed 5-iteration solves leave every rank's counters at 10 iterations"""
+    prm = params(golden, "a6_dcavity.par", imax=12, jmax=9, kmax=7, eps=0.0, itermax=5)
+    rng = np.random.default_rng(28)
+    p0, rhs = rng.standard_normal((9, 11, 14)), rng.standard_normal((9, 11, 14))
+    ns = orc3.NS3(prm)
+    ns.p[...] = p0
+    ns.rhs[...] = rhs
+    ref = [ns.solve(), ns.solve()]
+
+    def rank(r, cid):
+        with M.Grid3(prm, nranks=2, rank=r, comm_id=cid, dims=(2, 1, 1)) as g:
+            g.upload(M.P3, block(p0, g))
+            g.upload(M.RHS3, block(rhs, g))
+            g.enable_timing(True)
+            solves = [g.solve(), g.solve()]
+            return solves, g.solve_time(), g.gather(M.P3)
+
+    out = run_ranks(2, rank)
+    for solves, (ms, its), _ in out:
+        print("solves", solves, "oracle", ref, "solve_time", ms, its)
+        assert [s[0] for s in solves] == [s[0] for s in ref] == [5, 5]
+        assert its == 10 and ms > 0.0
+        assert [s[1] for s in solves] == [s[1] for s in out[0][0]]  # the all-reduced residual
+        for s, s_ref in zip(solves, ref):
+            assert s[1] == pytest.approx(s_ref[1], rel=1e-12)
+    assert np.array_equal(out[0][2], ns.p)
+
+
 @pytest.mark.parametrize("dims", [(2, 2, 2), (1, 2, 2)])
 def test_solve_converges_partition_independent(golden, dims):
     """the 33^3 fixture of the slab test (seed 11, eps 1e-4, two consecutive

@@ -212,6 +212,51 @@ def test_solve_itermax_zero_does_nothing(golden):
         assert np.array_equal(g.download(M.P3), st["p"])
 
 
+# the single-rank schedules of misor3_solve (SOLVE_TUNES' fields)
+EPILOGUE_PATHS = {"resident": (1, 8, 0, 1, 0, 1), "folded": (1, 8, 0, 1), "unfolded": (1, 8, 0, 0),
+                  "two_pass": (0, 8, 0)}
+_epilogue_runs = {}
+
+
+def timed_solves(golden, path):
+    """two timed 5-iteration solves at 12x9x7 on one schedule, run once per schedule:
+    ((it, res) of each, solve_time(), p), or the reason the schedule cannot run"""
+    if path not in _epilogue_runs:
+        prm = params(golden, "a6_dcavity.par", imax=12, jmax=9, kmax=7, eps=0.0, itermax=5)
+        st = random_state((9, 11, 14), 28)
+        tune = EPILOGUE_PATHS[path]
+        with M.Grid3(prm) as g:
+            set_tune(g, tune[:5])
+            if len(tune) > 5:
+                g.set_tuning(M.TUNE3_RESIDENT, tune[5])
+            if len(tune) > 5 and g.get_tuning(M.TUNE3_RESIDENT) != 1:
+                _epilogue_runs[path] = "the resident solve does not fit this device at 12x9x7"
+            else:
+                g.upload(M.P3, st["p"])
+                g.upload(M.RHS3, st["rhs"])
+                g.enable_timing(True)
+                solves = [g.solve(), g.solve()]
+                _epilogue_runs[path] = (solves, g.solve_time(), g.download(M.P3))
+    return _epilogue_runs[path]
+
+
+@pytest.mark.parametrize("path", sorted(EPILOGUE_PATHS))
+def test_solve_epilogue_counts_every_schedule_alike(golden, path):
+    """what every schedule of misor3_solve does after its loop: the iteration
+    count and residual it returns and the timing counters it adds to, tied to p
+    (which test_solve_fixed_iterations_bitwise fixes against the oracle)"""
+    run = timed_solves(golden, path)
+    if isinstance(run, str):
+        pytest.skip(run)
+    ref = timed_solves(golden, "two_pass")
+    solves, (ms, its), p = run
+    print(path, "solves", solves, "solve_time", ms, its)
+    assert [s[0] for s in solves] == [5, 5]
+    assert its == 10 and ms > 0.0
+    assert [s[1] for s in solves] == [s[1] for s in ref[0]]
+    assert np.array_equal(p, ref[2])
+
+
 def run_gpu(prm, steps, tune=None):
     """assignment-6/src/main.c:45-60 through the C ABI (no normalizePressure)"""
     g = M.Grid3(prm)

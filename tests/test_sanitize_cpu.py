@@ -2,7 +2,7 @@
 the reference's failure mode is fail-fast; here memory errors, leaks and UB
 in the CPU-side code are caught by a sanitized build).
 
-Three executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
+Four executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
 -fno-sanitize-recover=undefined):
   * bin/asan/host-check (practical-parallel-algorithms-with-mpi_amd/host/
     sanitize_main.c): the .par reader on every .par the tests use, the
@@ -11,6 +11,9 @@ Three executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
   * bin/asan/pass-plan-check (host/pass_plan_check.cc): the pass-plan
     arithmetic of the red-black solve loop (csrc/pass_plan.h), every plan of
     1..400 iterations in passes of 1..10, and the short plan's rule;
+  * bin/asan/decomp3-check (host/decomp3_check.cc): the 3D decompositions
+    (csrc/decomp3.h) -- process grids of 1..16 ranks, owned boxes and slab
+    gather ranges marked cell by cell, the refused cases, mutual neighbours;
   * oracle/_asan/oracle-check (oracle/sanitize_main.c): every oracle
     function on small ragged grids, with the reference's iteration KATs and
     multi-threaded == scalar bit identity.
@@ -50,6 +53,12 @@ def test_host_code_sanitized(tmp_path):
 def test_pass_plan_sanitized():
     build(PKG)
     out = run([os.path.join(PKG, "bin", "asan", "pass-plan-check")])
+    assert "all checks passed" in out
+
+
+def test_decomp3_sanitized():
+    build(PKG)
+    out = run([os.path.join(PKG, "bin", "asan", "decomp3-check")])
     assert "all checks passed" in out
 
 
