@@ -1,26 +1,15 @@
-// misor_api.hip -- the C ABI of include/misor.h, part 1: errors, the 2D
-// decomposition, grid lifecycle (create / destroy, streams), transfers
-// (upload / download / gather / exchange / fill / Poisson init), tuning and
-// statistics.  The solve loop is in misor_solve.hip, the NS step in
-// misor_ns.hip, communication in misor_comm.hip, launch plans in
-// misor_plan.hip; their shared state is struct misor_grid (misor_grid.h).
+// misor_api.hip -- the C ABI of include/misor.h, part 1: errors, grid lifecycle
+// (create / destroy, streams), transfers (upload / download / exchange / fill /
+// Poisson init, and gather's entry), tuning and statistics.  The decomposition
+// arithmetic is in decomp2.h, the solve loop in misor_solve.hip, the NS step in
+// misor_ns.hip, communication (gather's transport too) in misor_comm.hip,
+// launch plans in misor_plan.hip; their shared state is struct misor_grid
+// (misor_grid.h).
 
-#include "decomp3.h"  // size_of_rank
 #include "misor_grid.h"
 
 namespace {
-
 thread_local std::string g_err;
-
-// MPI_Dims_create(n, 2): the most balanced factorisation, larger factor first
-void dims_create(int n, int dims[2]) {
-    int best = 1;
-    for (int d = 1; d * d <= n; ++d)
-        if (n % d == 0) best = d;
-    dims[0] = n / best;
-    dims[1] = best;
-}
-
 }  // namespace
 
 int fail(int code, const char* fmt, ...) {
@@ -38,41 +27,13 @@ void misor::set_last_error(const char* msg) { g_err = msg; }
 const char* misor_last_error(void) { return g_err.c_str(); }
 const char* misor_version(void) { return "misor 0.1 (gfx950, fp64 red-black SOR)"; }
 
+// the decomposition itself is in decomp2.h; the row pitch is the device layout's
 int misor_decompose(int nranks, int rank, int imax, int jmax, const int dims_in[2],
                     misor_local* out) {
-    if (!out || nranks < 1 || rank < 0 || rank >= nranks || imax < 2 || jmax < 2)
-        return fail(MISOR_EINVAL, "misor_decompose: bad arguments");
-    int dims[2] = {0, 0};
-    if (dims_in && dims_in[0] > 0 && dims_in[1] > 0) {
-        dims[0] = dims_in[0];
-        dims[1] = dims_in[1];
-        if (dims[0] * dims[1] != nranks)
-            return fail(MISOR_EINVAL, "dims %dx%d != nranks %d", dims[0], dims[1], nranks);
-    } else {
-        dims_create(nranks, dims);
-    }
-    // MPI_Cart_create row-major rank order: coords = (rank / dims[1], rank % dims[1])
-    const int cx = rank / dims[1], cy = rank % dims[1];
-    misor_local L{};
-    L.dims[0] = dims[0];
-    L.dims[1] = dims[1];
-    L.coords[0] = cx;
-    L.coords[1] = cy;
-    L.ni = size_of_rank(cx, dims[0], imax);
-    L.nj = size_of_rank(cy, dims[1], jmax);
-    int io = 0, jo = 0;
-    for (int c = 0; c < cx; ++c) io += size_of_rank(c, dims[0], imax);
-    for (int c = 0; c < cy; ++c) jo += size_of_rank(c, dims[1], jmax);
-    L.ioff = io;
-    L.joff = jo;
-    auto rank_of = [&](int x, int y) { return x * dims[1] + y; };
-    L.neighbours[0] = cx > 0 ? rank_of(cx - 1, cy) : -1;            // left
-    L.neighbours[1] = cx < dims[0] - 1 ? rank_of(cx + 1, cy) : -1;  // right
-    L.neighbours[2] = cy > 0 ? rank_of(cx, cy - 1) : -1;            // bottom
-    L.neighbours[3] = cy < dims[1] - 1 ? rank_of(cx, cy + 1) : -1;  // top
-    if (L.ni < 2 || L.nj < 2) return fail(MISOR_EINVAL, "local block smaller than 2x2");
-    L.pitch = layout_pitch(L.ni);
-    *out = L;
+    char err[kDecompErr];
+    const int rc = decompose2(nranks, rank, imax, jmax, dims_in, out, err);
+    if (rc != MISOR_OK) return fail(rc, "%s", err);
+    out->pitch = layout_pitch(out->ni);
     return MISOR_OK;
 }
 
@@ -164,6 +125,144 @@ void misor_destroy(misor_grid* g) {
 
 int misor_create(misor_grid** out, const misor_desc* d) { return grid_create(out, d, false); }
 
+// grid_create's steps.  Each records its message through fail() and returns
+// its code; grid_create destroys the half-built grid.
+
+// the sweep's and the temporally blocked pass's geometry from the local block
+// and the desc
+static int set_geometry(misor_grid* g) {
+    const misor_desc* d = &g->desc;
+    const misor_local& L = g->loc;
+    SweepParams& sp = g->sp;
+    sp.pitch = g->pitch;
+    sp.ni = L.ni;
+    sp.nj = L.nj;
+    sp.parity = (L.ioff + L.joff) & 1;
+    sp.ghost_left = L.neighbours[0] < 0;
+    sp.ghost_right = L.neighbours[1] < 0;
+    sp.ghost_bottom = L.neighbours[2] < 0;
+    sp.ghost_top = L.neighbours[3] < 0;
+    sp.red_lo_i = sp.ghost_left ? 1 : 0;
+    sp.red_hi_i = sp.ghost_right ? L.ni : L.ni + 1;
+    sp.red_lo_j = sp.ghost_bottom ? 1 : 0;
+    sp.red_hi_j = sp.ghost_top ? L.nj : L.nj + 1;
+    const SorConsts sc = sor_consts(d->dx, d->dy, d->omega, d->variant);
+    sp.idx2 = sc.idx2;
+    sp.idy2 = sc.idy2;
+    sp.coef = sc.coef;
+    {
+        // power-of-two spacing (sor_tb.h resid<true>): 1/dx^2 == 1/dy^2 == 2^m, m >= 0
+        int e = 0;
+        const double mant = frexp(sp.idx2, &e);
+        sp.pow2 = sp.idx2 == sp.idy2 && mant == 0.5 && e >= 1;
+    }
+    if (configure_sweep(g, kDefaultSweepVariant, 0, 1) != MISOR_OK) return MISOR_ENOMEM;
+    {
+        // temporally blocked pass: same physics, its own geometry; every cell of
+        // a neighbour's 2T-deep halo is updated (identical arithmetic), only the
+        // physical sides are bounded
+        constexpr int kBig = 1 << 29;
+        SweepParams& tp = g->tp;
+        tp = sp;
+        tp.upd_lo_i = sp.ghost_left ? 1 : -kBig;
+        tp.upd_hi_i = sp.ghost_right ? L.ni : kBig;
+        tp.upd_lo_j = sp.ghost_bottom ? 1 : -kBig;
+        tp.upd_hi_j = sp.ghost_top ? L.nj : kBig;
+        // an interior block (overlapped pass) streams no halo cell of src
+        tp.int_lo_i = sp.ghost_left ? -kBig : 1;
+        tp.int_hi_i = sp.ghost_right ? kBig : L.ni;
+        tp.int_lo_j = sp.ghost_bottom ? -kBig : 1;
+        tp.int_hi_j = sp.ghost_top ? kBig : L.nj;
+    }
+    if (g->dist) {
+        // blocks whose footprint (rows j0-2..j1+1, columns c0-2..c_end+1) stays clear
+        // of the halo on neighbour sides AND of the 2-deep send region can sweep
+        // while the exchange is in flight
+        sp.int_lo_i = L.neighbours[0] >= 0 ? 3 : -1000000000;
+        sp.int_hi_i = L.neighbours[1] >= 0 ? L.ni - 2 : 2000000000;
+        sp.int_lo_j = L.neighbours[2] >= 0 ? 3 : -1000000000;
+        sp.int_hi_j = L.neighbours[3] >= 0 ? L.nj - 2 : 2000000000;
+    }
+    return MISOR_OK;
+}
+
+// the loop state and the reduction buffers
+static int alloc_state(misor_grid* g) {
+    if (hipMalloc(&g->tb_queue, 16 * sizeof(int)) != hipSuccess ||
+        hipMemsetAsync(g->tb_queue, 0, 16 * sizeof(int), g->stream) != hipSuccess ||
+        hipMalloc(&g->st, sizeof(DevState)) != hipSuccess ||
+        hipHostMalloc(&g->st_host, sizeof(DevState), hipHostMallocDefault) != hipSuccess)
+        return fail(MISOR_ENOMEM, "state allocation failed");
+    const int rb = reduce_blocks(g->loc.ni, g->loc.nj);
+    if (hipMalloc(&g->red_partials, sizeof(double) * 2 * rb) != hipSuccess ||
+        hipMalloc(&g->max_partials, sizeof(double) * 2 * rb) != hipSuccess ||
+        hipMalloc(&g->red_out, sizeof(double) * 4) != hipSuccess ||
+        hipHostMalloc(&g->red_host, sizeof(double) * 4, hipHostMallocDefault) != hipSuccess)
+        return fail(MISOR_ENOMEM, "reduction allocation failed");
+    return MISOR_OK;
+}
+
+// a decomposed grid's transport: neighbour table, halo plans, communication
+// stream and events, halo buffers, and the in-process group or RCCL
+static int comm_setup(misor_grid* g, bool proxy) {
+    const misor_desc* d = &g->desc;
+    const misor_local& L = g->loc;
+    if (!d->comm_id) return fail(MISOR_EINVAL, "nranks > 1 needs comm_id");
+    neighbours8(L.dims, L.coords, g->nbr);
+    if (proxy) {  // (MISOR_PROXY_SIDES: every neighbour is rank 0; corners where both sides have one)
+        const int* nb = L.neighbours;
+        const int pn[kDirs] = {nb[0], nb[1], nb[2], nb[3],
+                               nb[0] >= 0 && nb[2] >= 0 ? 0 : -1,
+                               nb[1] >= 0 && nb[2] >= 0 ? 0 : -1,
+                               nb[0] >= 0 && nb[3] >= 0 ? 0 : -1,
+                               nb[1] >= 0 && nb[3] >= 0 ? 0 : -1};
+        for (int k = 0; k < kDirs; ++k) g->nbr[k] = pn[k];
+    }
+    // halo plans up to depth 2*kMaxT + 1 (the skewed split ring's), as deep
+    // as the smallest block allows
+    g->max_depth = max_halo_depth(d->imax, d->jmax, L.dims);
+    long long maxtot = 1;
+    for (int dd = 1; dd <= g->max_depth; ++dd) {
+        g->plan[dd] = halo_plan(L.ni, L.nj, g->nbr, dd);
+        maxtot = std::max(maxtot, g->plan[dd].total);
+    }
+    // communication and edge blocks at high priority: their workgroups are
+    // dispatched ahead of queued interior blocks as slots free up
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    bool ok = hipStreamCreateWithPriority(&g->cstream, hipStreamNonBlocking, prio_hi) ==
+              hipSuccess;
+    for (hipEvent_t* e : {&g->ev_s, &g->ev_x, &g->ev_i[0], &g->ev_i[1], &g->ev_e2[0],
+                          &g->ev_e2[1], &g->ev_dk[0], &g->ev_dk[1]})
+        ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (!ok) return fail(MISOR_EHIP, "comm stream/event creation failed");
+    const size_t hb = (size_t)maxtot * sizeof(double);
+    if (hipMalloc(&g->sendbuf, hb) != hipSuccess || hipMalloc(&g->recvbuf, hb) != hipSuccess)
+        return fail(MISOR_ENOMEM, "halo buffer allocation failed");
+    char name[MISOR_COMM_ID_BYTES + 1];
+    // (no host scratch: this all-reduce stages on the device, la_stage / la_gather)
+    const LocalJoin joined =
+        join_local_group(d->comm_id, d->nranks, d->rank, g, 0, g->local, name);
+    if (joined == LocalJoin::kBadMember)
+        return fail(MISOR_EINVAL, "local group %s: bad rank/size", name);
+    if (joined == LocalJoin::kJoined) {
+        bool lok = hipMalloc(&g->la_stage, sizeof(double) * 2 * kMaxT) == hipSuccess &&
+                   hipMalloc(&g->la_gather, sizeof(double) * 2 * kMaxT * (size_t)d->nranks) ==
+                       hipSuccess;
+        for (hipEvent_t* e : {&g->lx_pk, &g->lx_cp, &g->la_val[0], &g->la_val[1],
+                              &g->la_rd[0], &g->la_rd[1], &g->la_cmb[0], &g->la_cmb[1]})
+            lok = lok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+        g->local->barrier();  // every member registered before any exchange
+        if (!lok) return fail(MISOR_EHIP, "in-process transport allocation failed");
+    } else {
+        ncclUniqueId id;
+        memcpy(&id, d->comm_id, sizeof id);
+        if (ncclCommInitRank(&g->comm, d->nranks, id, d->rank) != ncclSuccess)
+            return fail(MISOR_ECOMM, "ncclCommInitRank failed");
+    }
+    return MISOR_OK;
+}
+
 int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
     if (!out || !d) return fail(MISOR_EINVAL, "null argument");
     *out = nullptr;
@@ -221,6 +320,14 @@ int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
         misor_destroy(g);               \
         return c_;                      \
     } while (0)
+#define CREATE_STEP(x)        \
+    do {                      \
+        const int c_ = (x);   \
+        if (c_) {             \
+            misor_destroy(g); \
+            return c_;        \
+        }                     \
+    } while (0)
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess)
         CREATE_FAIL(MISOR_EHIP, "hipStreamCreate failed");
     g->own_stream = true;
@@ -237,136 +344,14 @@ int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
             hipSuccess)
             CREATE_FAIL(MISOR_EHIP, "hipMemset failed");
     }
-
-    // sweep configuration
-    SweepParams& sp = g->sp;
-    sp.pitch = g->pitch;
-    sp.ni = L.ni;
-    sp.nj = L.nj;
-    sp.parity = (L.ioff + L.joff) & 1;
-    sp.ghost_left = L.neighbours[0] < 0;
-    sp.ghost_right = L.neighbours[1] < 0;
-    sp.ghost_bottom = L.neighbours[2] < 0;
-    sp.ghost_top = L.neighbours[3] < 0;
-    sp.red_lo_i = sp.ghost_left ? 1 : 0;
-    sp.red_hi_i = sp.ghost_right ? L.ni : L.ni + 1;
-    sp.red_lo_j = sp.ghost_bottom ? 1 : 0;
-    sp.red_hi_j = sp.ghost_top ? L.nj : L.nj + 1;
-    const SorConsts sc = sor_consts(d->dx, d->dy, d->omega, d->variant);
-    sp.idx2 = sc.idx2;
-    sp.idy2 = sc.idy2;
-    sp.coef = sc.coef;
-    {
-        // power-of-two spacing (sor_tb.h resid<true>): 1/dx^2 == 1/dy^2 == 2^m, m >= 0
-        int e = 0;
-        const double mant = frexp(sp.idx2, &e);
-        sp.pow2 = sp.idx2 == sp.idy2 && mant == 0.5 && e >= 1;
-    }
-    if (configure_sweep(g, kDefaultSweepVariant, 0, 1) != MISOR_OK) {
-        misor_destroy(g);
-        return MISOR_ENOMEM;
-    }
-    {
-        // temporally blocked pass: same physics, its own geometry; every cell of
-        // a neighbour's 2T-deep halo is updated (identical arithmetic), only the
-        // physical sides are bounded
-        constexpr int kBig = 1 << 29;
-        SweepParams& tp = g->tp;
-        tp = sp;
-        tp.upd_lo_i = sp.ghost_left ? 1 : -kBig;
-        tp.upd_hi_i = sp.ghost_right ? L.ni : kBig;
-        tp.upd_lo_j = sp.ghost_bottom ? 1 : -kBig;
-        tp.upd_hi_j = sp.ghost_top ? L.nj : kBig;
-        // an interior block (overlapped pass) streams no halo cell of src
-        tp.int_lo_i = sp.ghost_left ? -kBig : 1;
-        tp.int_hi_i = sp.ghost_right ? kBig : L.ni;
-        tp.int_lo_j = sp.ghost_bottom ? -kBig : 1;
-        tp.int_hi_j = sp.ghost_top ? kBig : L.nj;
-    }
-    if (hipMalloc(&g->tb_queue, 16 * sizeof(int)) != hipSuccess ||
-        hipMemsetAsync(g->tb_queue, 0, 16 * sizeof(int), g->stream) != hipSuccess ||
-        hipMalloc(&g->st, sizeof(DevState)) != hipSuccess ||
-        hipHostMalloc(&g->st_host, sizeof(DevState), hipHostMallocDefault) != hipSuccess)
-        CREATE_FAIL(MISOR_ENOMEM, "state allocation failed");
-    const int rb = reduce_blocks(L.ni, L.nj);
-    if (hipMalloc(&g->red_partials, sizeof(double) * 2 * rb) != hipSuccess ||
-        hipMalloc(&g->max_partials, sizeof(double) * 2 * rb) != hipSuccess ||
-        hipMalloc(&g->red_out, sizeof(double) * 4) != hipSuccess ||
-        hipHostMalloc(&g->red_host, sizeof(double) * 4, hipHostMallocDefault) != hipSuccess)
-        CREATE_FAIL(MISOR_ENOMEM, "reduction allocation failed");
-
-    if (g->dist) {
-        if (!d->comm_id) CREATE_FAIL(MISOR_EINVAL, "nranks > 1 needs comm_id");
-        const int cx = L.coords[0], cy = L.coords[1], dx_ = L.dims[0], dy_ = L.dims[1];
-        auto at = [&](int x, int y) {
-            return (x >= 0 && x < dx_ && y >= 0 && y < dy_) ? x * dy_ + y : -1;
-        };
-        const int nbrs[kDirs] = {at(cx - 1, cy),     at(cx + 1, cy),     at(cx, cy - 1),
-                                 at(cx, cy + 1),     at(cx - 1, cy - 1), at(cx + 1, cy - 1),
-                                 at(cx - 1, cy + 1), at(cx + 1, cy + 1)};
-        for (int k = 0; k < kDirs; ++k) g->nbr[k] = nbrs[k];
-        if (proxy) {  // (MISOR_PROXY_SIDES: every neighbour is rank 0; corners where both sides have one)
-            const int* nb = L.neighbours;
-            const int pn[kDirs] = {nb[0], nb[1], nb[2], nb[3],
-                                   nb[0] >= 0 && nb[2] >= 0 ? 0 : -1,
-                                   nb[1] >= 0 && nb[2] >= 0 ? 0 : -1,
-                                   nb[0] >= 0 && nb[3] >= 0 ? 0 : -1,
-                                   nb[1] >= 0 && nb[3] >= 0 ? 0 : -1};
-            for (int k = 0; k < kDirs; ++k) g->nbr[k] = pn[k];
-        }
-        // halo plans up to depth 2*kMaxT + 1 (the skewed split ring's), as deep
-        // as the smallest block allows
-        const int minb = std::min(d->imax / L.dims[0], d->jmax / L.dims[1]);
-        g->max_depth = std::max(2, std::min(2 * kMaxT + 1, minb));
-        for (int dd = 1; dd <= g->max_depth; ++dd) build_plan(g, dd);
-        // communication and edge blocks at high priority: their workgroups are
-        // dispatched ahead of queued interior blocks as slots free up
-        int prio_lo = 0, prio_hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-        bool ok = hipStreamCreateWithPriority(&g->cstream, hipStreamNonBlocking, prio_hi) ==
-                  hipSuccess;
-        for (hipEvent_t* e : {&g->ev_s, &g->ev_x, &g->ev_i[0], &g->ev_i[1], &g->ev_e2[0],
-                              &g->ev_e2[1], &g->ev_dk[0], &g->ev_dk[1]})
-            ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-        if (!ok) CREATE_FAIL(MISOR_EHIP, "comm stream/event creation failed");
-        // blocks whose footprint (rows j0-2..j1+1, columns c0-2..c_end+1) stays clear
-        // of the halo on neighbour sides AND of the 2-deep send region can sweep
-        // while the exchange is in flight
-        sp.int_lo_i = L.neighbours[0] >= 0 ? 3 : -1000000000;
-        sp.int_hi_i = L.neighbours[1] >= 0 ? L.ni - 2 : 2000000000;
-        sp.int_lo_j = L.neighbours[2] >= 0 ? 3 : -1000000000;
-        sp.int_hi_j = L.neighbours[3] >= 0 ? L.nj - 2 : 2000000000;
-        long long maxtot = 1;
-        for (int dd = 1; dd <= g->max_depth; ++dd) maxtot = std::max(maxtot, g->plan[dd].total);
-        const size_t hb = (size_t)maxtot * sizeof(double);
-        if (hipMalloc(&g->sendbuf, hb) != hipSuccess || hipMalloc(&g->recvbuf, hb) != hipSuccess)
-            CREATE_FAIL(MISOR_ENOMEM, "halo buffer allocation failed");
-        char name[MISOR_COMM_ID_BYTES + 1];
-        // (no host scratch: this all-reduce stages on the device, la_stage / la_gather)
-        const LocalJoin joined =
-            join_local_group(d->comm_id, nranks, d->rank, g, 0, g->local, name);
-        if (joined == LocalJoin::kBadMember)
-            CREATE_FAIL(MISOR_EINVAL, "local group %s: bad rank/size", name);
-        if (joined == LocalJoin::kJoined) {
-            bool lok = hipMalloc(&g->la_stage, sizeof(double) * 2 * kMaxT) == hipSuccess &&
-                       hipMalloc(&g->la_gather, sizeof(double) * 2 * kMaxT * (size_t)nranks) ==
-                           hipSuccess;
-            for (hipEvent_t* e : {&g->lx_pk, &g->lx_cp, &g->la_val[0], &g->la_val[1],
-                                  &g->la_rd[0], &g->la_rd[1], &g->la_cmb[0], &g->la_cmb[1]})
-                lok = lok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-            g->local->barrier();  // every member registered before any exchange
-            if (!lok) CREATE_FAIL(MISOR_EHIP, "in-process transport allocation failed");
-        } else {
-            ncclUniqueId id;
-            memcpy(&id, d->comm_id, sizeof id);
-            if (ncclCommInitRank(&g->comm, nranks, id, d->rank) != ncclSuccess)
-                CREATE_FAIL(MISOR_ECOMM, "ncclCommInitRank failed");
-        }
-    }
+    CREATE_STEP(set_geometry(g));
+    CREATE_STEP(alloc_state(g));
+    if (g->dist) CREATE_STEP(comm_setup(g, proxy));
     if (configure_tb(g, default_tsteps(g, kDefaultTbVariant), kDefaultTbVariant, 0) != MISOR_OK)
         CREATE_FAIL(MISOR_ENOMEM, "%s", g_err.c_str());
     if (hipStreamSynchronize(g->stream) != hipSuccess)
         CREATE_FAIL(MISOR_EHIP, "hipStreamSynchronize failed");
+#undef CREATE_STEP
 #undef CREATE_FAIL
     *out = g;
     return MISOR_OK;
@@ -416,8 +401,18 @@ static double* field_ptr(misor_grid* g, int field) {
     }
 }
 
-static double* origin(misor_grid* g, double* base) {
-    return base + (long long)kYOff * g->pitch + kXOff;  // cell (0,0)
+// `field` was written from outside (upload, fill, initialisation, adoption):
+// what the grid derived from its old contents no longer holds.  A write of P
+// goes to every pressure buffer -- corners and ghosts must agree, and its halo
+// is the caller's -- so the first one is current again.
+static void note_write(misor_grid* g, int field) {
+    if (field == MISOR_RHS) g->rhs_halo = 0;
+    if (field == MISOR_U || field == MISOR_V) ++g->uv_ver;
+    if (field == MISOR_F || field == MISOR_G || field == MISOR_RHS) ++g->fgr_ver;
+    if (field == MISOR_P) {
+        g->cur = 0;
+        g->p_stale = false;
+    }
 }
 
 int misor_upload(misor_grid* g, int field, const double* host) {
@@ -425,12 +420,8 @@ int misor_upload(misor_grid* g, int field, const double* host) {
     HIPCHK(hipSetDevice(g->device));
     const size_t w = (size_t)(g->loc.ni + 2) * sizeof(double);
     const size_t h = (size_t)(g->loc.nj + 2);
-    if (field == MISOR_RHS) g->rhs_halo = 0;
-    if (field == MISOR_U || field == MISOR_V) ++g->uv_ver;
-    if (field == MISOR_F || field == MISOR_G || field == MISOR_RHS) ++g->fgr_ver;
-    if (field == MISOR_P) {  // every pressure buffer: corners and ghosts must agree
-        g->cur = 0;
-        g->p_stale = false;  // (the caller's halo)
+    note_write(g, field);
+    if (field == MISOR_P) {
         for (int b = 0; b < g->np; ++b)
             HIPCHK(hipMemcpy2DAsync(origin(g, pbuf(g, b)), g->pitch * sizeof(double), host,
                                     w, w, h, hipMemcpyHostToDevice, g->stream));
@@ -453,10 +444,8 @@ int grid_adopt(misor_grid* g, const double* p_dev, const double* rhs_dev, double
     g->desc.itermax = itermax;
     g->sp.coef = g->tp.coef = sor_consts(g->desc.dx, g->desc.dy, omega, g->desc.variant).coef;
     const size_t bytes = (size_t)g->elems * sizeof(double);
-    g->cur = 0;
-    g->p_stale = false;
-    g->rhs_halo = 0;
-    ++g->fgr_ver;
+    note_write(g, MISOR_P);
+    note_write(g, MISOR_RHS);
     for (int b = 0; b < g->np; ++b)
         HIPCHK(hipMemcpyAsync(pbuf(g, b), p_dev, bytes, hipMemcpyDeviceToDevice, g->stream));
     HIPCHK(hipMemcpyAsync(g->fld[kRhs], rhs_dev, bytes, hipMemcpyDeviceToDevice, g->stream));
@@ -491,125 +480,13 @@ int misor_download(misor_grid* g, int field, double* host) {
     return MISOR_OK;
 }
 
-// The block a rank contributes to the assembled global field: its interior
-// plus the ghost layer on its physical sides (assembleResult,
-// assignment-5/skeleton/src/solver.c:234-300), in local indices.
-struct OwnedBlock {
-    int i0, j0, w, h;    // first local cell and extent
-    int gi0, gj0;        // first global cell
-};
-static OwnedBlock owned_block(const misor_local& L) {
-    OwnedBlock b{};
-    b.i0 = L.neighbours[0] < 0 ? 0 : 1;
-    b.j0 = L.neighbours[2] < 0 ? 0 : 1;
-    const int i1 = L.neighbours[1] < 0 ? L.ni + 1 : L.ni;
-    const int j1 = L.neighbours[3] < 0 ? L.nj + 1 : L.nj;
-    b.w = i1 - b.i0 + 1;
-    b.h = j1 - b.j0 + 1;
-    b.gi0 = L.ioff + b.i0;
-    b.gj0 = L.joff + b.j0;
-    return b;
-}
-
 int misor_gather(misor_grid* g, int field, double* host) {
     if (!g || !field_ptr(g, field)) return fail(MISOR_EINVAL, "bad gather");
     PROXYCHK(g);
     const int rank = g->dist ? g->desc.rank : 0;
     if (rank == 0 && !host) return fail(MISOR_EINVAL, "gather: rank 0 needs the global array");
     if (g->desc.nranks == 1) return misor_download(g, field, host);
-    HIPCHK(hipSetDevice(g->device));
-    const size_t gw = (size_t)(g->desc.imax + 2);  // global row length (doubles)
-    const OwnedBlock mine = owned_block(g->loc);
-    // every rank packs its block contiguously (a strided 2D copy on the device)
-    long long need = (long long)(g->loc.ni + 2) * (g->loc.nj + 2);
-    if (rank == 0) {
-        for (int r = 0; r < g->desc.nranks; ++r) {
-            misor_local L{};
-            int rc = misor_decompose(g->desc.nranks, r, g->desc.imax, g->desc.jmax,
-                                     g->loc.dims, &L);
-            if (rc) return rc;
-            need = std::max(need, (long long)(L.ni + 2) * (L.nj + 2));
-        }
-    }
-    // every rank allocates its packing buffer (rank 0: large enough for any
-    // rank's block -- it is also the receive stage); all ranks agree on the
-    // outcome before any send / receive is posted, so a failed allocation is
-    // an error on every rank instead of a rank blocked in a send
-    int alloc_ok = 1;
-    if (need > g->gbuf_cap) {
-        (void)hipFree(g->gbuf);
-        g->gbuf = nullptr;
-        g->gbuf_cap = 0;
-        if (hipMalloc(&g->gbuf, sizeof(double) * (size_t)need) == hipSuccess)
-            g->gbuf_cap = need;
-        else
-            alloc_ok = 0;
-    }
-    {
-        g->red_host[3] = alloc_ok ? 0.0 : 1.0;
-        HIPCHK(hipMemcpyAsync(g->red_out + 3, g->red_host + 3, sizeof(double),
-                              hipMemcpyHostToDevice, g->stream));
-        int rc = allreduce(g, g->red_out + 3, 1, 1);
-        if (rc) return rc;
-        HIPCHK(hipMemcpyAsync(g->red_host + 3, g->red_out + 3, sizeof(double),
-                              hipMemcpyDeviceToHost, g->stream));
-        MISOR_TRY(wait_stream(g, g->stream));
-        if (g->red_host[3] != 0.0)
-            return fail(MISOR_ENOMEM, "gather: a rank could not allocate its %s buffer",
-                        alloc_ok ? "peer's" : "own");
-    }
-    const double* f = field_ptr(g, field);
-    const double* src = origin(g, const_cast<double*>(f)) + (long long)mine.j0 * g->pitch + mine.i0;
-    HIPCHK(hipMemcpy2DAsync(g->gbuf, sizeof(double) * mine.w, src, sizeof(double) * g->pitch,
-                            sizeof(double) * mine.w, mine.h, hipMemcpyDeviceToDevice, g->stream));
-    MISOR_TRY(wait_stream(g, g->stream));
-    auto to_host = [&](const double* dev, const OwnedBlock& b) -> int {
-        HIPCHK(hipMemcpy2DAsync(host + (size_t)b.gj0 * gw + b.gi0, sizeof(double) * gw, dev,
-                                sizeof(double) * b.w, sizeof(double) * b.w, b.h,
-                                hipMemcpyDeviceToHost, g->stream));
-        MISOR_TRY(wait_stream(g, g->stream));
-        return MISOR_OK;
-    };
-    if (g->local) {
-        g->local->barrier();  // every block packed
-        if (rank == 0) {
-            for (int r = 0; r < g->desc.nranks; ++r) {
-                const misor_grid* q = g->local->members[r];
-                const OwnedBlock b = owned_block(q->loc);
-                int rc = to_host(q->gbuf, b);  // unified addressing: any member's device
-                if (rc) return rc;
-            }
-        }
-        g->local->barrier();  // nobody repacks before rank 0 has read
-        return MISOR_OK;
-    }
-    // RCCL: rank r sends its packed block to rank 0, one peer at a time; rank
-    // 0 receives into its own packing buffer once its block is on the host
-    double* const stage = g->gbuf;
-    if (rank == 0) {
-        int rc = to_host(g->gbuf, mine);
-        if (rc) return rc;
-    }
-    int rc = MISOR_OK;
-    for (int r = 1; r < g->desc.nranks && rc == MISOR_OK; ++r) {
-        misor_local L{};
-        rc = misor_decompose(g->desc.nranks, r, g->desc.imax, g->desc.jmax, g->loc.dims, &L);
-        if (rc) break;
-        const OwnedBlock b = owned_block(L);
-        const size_t count = (size_t)b.w * b.h;
-        if (rank == r) {
-            if (ncclSend(g->gbuf, count, ncclDouble, 0, g->comm, g->stream) != ncclSuccess)
-                rc = fail(MISOR_ECOMM, "gather: ncclSend failed");
-        } else if (rank == 0) {
-            if (ncclRecv(stage, count, ncclDouble, r, g->comm, g->stream) != ncclSuccess)
-                rc = fail(MISOR_ECOMM, "gather: ncclRecv failed");
-            else
-                rc = to_host(stage, b);
-        }
-    }
-    if (rc) return rc;
-    MISOR_TRY(wait_stream(g, g->stream));
-    return MISOR_OK;
+    return gather(g, field_ptr(g, field), host);
 }
 
 int misor_exchange(misor_grid* g, int field, int depth) {
@@ -649,12 +526,8 @@ int misor_fill(misor_grid* g, int field, double value) {
     if (!g || !field_ptr(g, field)) return fail(MISOR_EINVAL, "bad fill");
     HIPCHK(hipSetDevice(g->device));
     // whole padded array: ghosts included, pads too (pads never feed results)
-    if (field == MISOR_RHS) g->rhs_halo = 0;
-    if (field == MISOR_U || field == MISOR_V) ++g->uv_ver;
-    if (field == MISOR_F || field == MISOR_G || field == MISOR_RHS) ++g->fgr_ver;
+    note_write(g, field);
     if (field == MISOR_P) {
-        g->cur = 0;
-        g->p_stale = false;
         for (int b = 0; b < g->np; ++b) launch_fill(g->stream, pbuf(g, b), g->elems, value);
     } else {
         launch_fill(g->stream, field_ptr(g, field), g->elems, value);
@@ -690,10 +563,8 @@ int misor_poisson_init(misor_grid* g, double xlength, double ylength, int proble
     HIPCHK(hipMalloc(&tab, host.size() * sizeof(double)));
     HIPCHK(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice,
                           g->stream));
-    g->cur = 0;
-    g->p_stale = false;
-    g->rhs_halo = 0;
-    ++g->fgr_ver;
+    note_write(g, MISOR_P);
+    note_write(g, MISOR_RHS);
     for (int b = 0; b < g->np; ++b)
         launch_poisson_init(g->stream, pbuf(g, b), g->fld[kRhs], tab, tab + 2 * (ni + 2),
                             tab + (ni + 2), ni, nj, g->pitch, problem);

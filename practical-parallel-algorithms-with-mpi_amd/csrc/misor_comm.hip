@@ -1,41 +1,9 @@
-// misor_comm.hip -- communication of a decomposed grid: the 8-neighbour halo
-// plans, the depth-d exchange and the all-reduce, over RCCL or the in-process
-// transport (LOCAL: groups), with a progress timeout (misor_grid.h).
+// misor_comm.hip -- communication of a decomposed grid: the depth-d halo
+// exchange, the all-reduce and the gather to rank 0, over RCCL or the
+// in-process transport (LOCAL: groups), with a progress timeout (misor_grid.h).
+// Who sends which cells to whom is decided in decomp2.h.
 
 #include "misor_grid.h"
-
-// Regions of the 8-neighbour exchange at halo depth d.  A rank sends the
-// cells it owns (interior, plus ghost cells on its physical sides) next to each
-// neighbour; ranks in one process row share nj and their physical top/bottom,
-// ranks in one process column share ni, so send and receive extents match.
-void build_plan(misor_grid* g, int d) {
-    const int ni = g->loc.ni, nj = g->loc.nj;
-    const int* nb = g->nbr;
-    const int cl = nb[0] >= 0 ? 1 : 0, ch = nb[1] >= 0 ? ni : ni + 1;
-    const int rl = nb[2] >= 0 ? 1 : 0, rh = nb[3] >= 0 ? nj : nj + 1;
-    HaloRegion S[kDirs] = {
-        {1, rl, d, rh - rl + 1, 0},      {ni - d + 1, rl, d, rh - rl + 1, 0},
-        {cl, 1, ch - cl + 1, d, 0},      {cl, nj - d + 1, ch - cl + 1, d, 0},
-        {1, 1, d, d, 0},                 {ni - d + 1, 1, d, d, 0},
-        {1, nj - d + 1, d, d, 0},        {ni - d + 1, nj - d + 1, d, d, 0}};
-    HaloRegion R[kDirs] = {
-        {1 - d, rl, d, rh - rl + 1, 0},  {ni + 1, rl, d, rh - rl + 1, 0},
-        {cl, 1 - d, ch - cl + 1, d, 0},  {cl, nj + 1, ch - cl + 1, d, 0},
-        {1 - d, 1 - d, d, d, 0},         {ni + 1, 1 - d, d, d, 0},
-        {1 - d, nj + 1, d, d, 0},        {ni + 1, nj + 1, d, d, 0}};
-    HaloPlan& P = g->plan[d];
-    long long so = 0, ro = 0;
-    for (int k = 0; k < kDirs; ++k) {
-        if (nb[k] < 0) S[k].w = S[k].h = R[k].w = R[k].h = 0;
-        S[k].off = so;
-        R[k].off = ro;
-        so += (long long)S[k].w * S[k].h;
-        ro += (long long)R[k].w * R[k].h;
-        P.send[k] = S[k];
-        P.recv[k] = R[k];
-    }
-    P.total = so > ro ? so : ro;
-}
 
 // a start/stop event pair for timing one communication step (kind 0: halo
 // exchange, 1: all-reduce) of the current batch; false when not timing
@@ -224,5 +192,97 @@ int allreduce(misor_grid* g, double* dev, int n, int is_max, hipStream_t s) {
     }
     NCCLCHK(ncclAllReduce(dev, dev, n, ncclDouble, is_max ? ncclMax : ncclSum, g->comm, s));
     if (timed) HIPCHK(hipEventRecord(t1, s));
+    return MISOR_OK;
+}
+
+// the block of every rank of g's decomposition, in rank order
+static int peer_blocks(const misor_grid* g, std::vector<misor_local>& peers) {
+    char err[kDecompErr];
+    peers.resize((size_t)g->desc.nranks);
+    for (int r = 0; r < g->desc.nranks; ++r) {
+        const int rc = decompose2(g->desc.nranks, r, g->desc.imax, g->desc.jmax, g->loc.dims,
+                                  &peers[r], err);
+        if (rc) return fail(rc, "%s", err);
+    }
+    return MISOR_OK;
+}
+
+// misor_gather on more than one rank: `field` (device, one of g's) assembled
+// into rank 0's global array `host`
+int gather(misor_grid* g, const double* field, double* host) {
+    HIPCHK(hipSetDevice(g->device));
+    const int rank = g->desc.rank, nranks = g->desc.nranks;
+    const size_t gw = (size_t)(g->desc.imax + 2);  // global row length (doubles)
+    const OwnedBlock mine = owned_block(g->loc);
+    // every rank packs its block contiguously (a strided 2D copy on the device)
+    long long need = (long long)(g->loc.ni + 2) * (g->loc.nj + 2);
+    std::vector<misor_local> peers;  // rank 0: whose block is which
+    if (rank == 0) {
+        MISOR_TRY(peer_blocks(g, peers));
+        for (const misor_local& L : peers)
+            need = std::max(need, (long long)(L.ni + 2) * (L.nj + 2));
+    }
+    // every rank allocates its packing buffer (rank 0: large enough for any
+    // rank's block -- it is also the receive stage); all ranks agree on the
+    // outcome before any send / receive is posted, so a failed allocation is
+    // an error on every rank instead of a rank blocked in a send
+    int alloc_ok = 1;
+    if (need > g->gbuf_cap) {
+        (void)hipFree(g->gbuf);
+        g->gbuf = nullptr;
+        g->gbuf_cap = 0;
+        if (hipMalloc(&g->gbuf, sizeof(double) * (size_t)need) == hipSuccess)
+            g->gbuf_cap = need;
+        else
+            alloc_ok = 0;
+    }
+    {
+        g->red_host[3] = alloc_ok ? 0.0 : 1.0;
+        HIPCHK(hipMemcpyAsync(g->red_out + 3, g->red_host + 3, sizeof(double),
+                              hipMemcpyHostToDevice, g->stream));
+        MISOR_TRY(allreduce(g, g->red_out + 3, 1, 1));
+        HIPCHK(hipMemcpyAsync(g->red_host + 3, g->red_out + 3, sizeof(double),
+                              hipMemcpyDeviceToHost, g->stream));
+        MISOR_TRY(wait_stream(g, g->stream));
+        if (g->red_host[3] != 0.0)
+            return fail(MISOR_ENOMEM, "gather: a rank could not allocate its %s buffer",
+                        alloc_ok ? "peer's" : "own");
+    }
+    const double* src = origin(g, const_cast<double*>(field)) + (long long)mine.j0 * g->pitch +
+                        mine.i0;
+    HIPCHK(hipMemcpy2DAsync(g->gbuf, sizeof(double) * mine.w, src, sizeof(double) * g->pitch,
+                            sizeof(double) * mine.w, mine.h, hipMemcpyDeviceToDevice, g->stream));
+    MISOR_TRY(wait_stream(g, g->stream));
+    auto to_host = [&](const double* dev, const OwnedBlock& b) -> int {
+        HIPCHK(hipMemcpy2DAsync(host + (size_t)b.gj0 * gw + b.gi0, sizeof(double) * gw, dev,
+                                sizeof(double) * b.w, sizeof(double) * b.w, b.h,
+                                hipMemcpyDeviceToHost, g->stream));
+        MISOR_TRY(wait_stream(g, g->stream));
+        return MISOR_OK;
+    };
+    if (g->local) {
+        g->local->barrier();  // every block packed
+        if (rank == 0)        // unified addressing: any member's device
+            for (int r = 0; r < nranks; ++r)
+                MISOR_TRY(to_host(g->local->members[r]->gbuf, owned_block(peers[r])));
+        g->local->barrier();  // nobody repacks before rank 0 has read
+        return MISOR_OK;
+    }
+    // RCCL: rank r sends its packed block to rank 0, one peer at a time; rank
+    // 0 receives into its own packing buffer once its block is on the host
+    if (rank == 0) {
+        MISOR_TRY(to_host(g->gbuf, mine));
+        for (int r = 1; r < nranks; ++r) {
+            const OwnedBlock b = owned_block(peers[r]);
+            if (ncclRecv(g->gbuf, (size_t)b.w * b.h, ncclDouble, r, g->comm, g->stream) !=
+                ncclSuccess)
+                return fail(MISOR_ECOMM, "gather: ncclRecv failed");
+            MISOR_TRY(to_host(g->gbuf, b));
+        }
+    } else if (ncclSend(g->gbuf, (size_t)mine.w * mine.h, ncclDouble, 0, g->comm, g->stream) !=
+               ncclSuccess) {
+        return fail(MISOR_ECOMM, "gather: ncclSend failed");
+    }
+    MISOR_TRY(wait_stream(g, g->stream));
     return MISOR_OK;
 }

@@ -1,8 +1,9 @@
 // misor_grid.h -- the host-side state of a grid (struct misor_grid) and what
-// the C-ABI units share: misor_api.hip (lifecycle, transfers, gather, tuning,
-// statistics), misor_comm.hip (halo exchange and all-reduce over RCCL or the
-// in-process transport), misor_plan.hip (launch geometry, chained-pass
+// the C-ABI units share: misor_api.hip (errors, lifecycle, transfers, tuning,
+// statistics), misor_comm.hip (halo exchange, all-reduce and gather over RCCL
+// or the in-process transport), misor_plan.hip (launch geometry, chained-pass
 // plans), misor_solve.hip (the solve loop) and misor_ns.hip (the NS step).
+// The 2D decomposition and the halo plans are plain arithmetic in decomp2.h.
 // Internal: nothing here is part of include/misor.h.
 #pragma once
 
@@ -135,7 +136,7 @@ struct misor_grid {
     bool dist = false;
     ncclComm_t comm = nullptr;
     int nbr[kDirs] = {-1, -1, -1, -1, -1, -1, -1, -1};  // L R B T BL BR TL TR
-    HaloPlan plan[2 * kMaxT + 2] = {};                   // by halo depth 1 .. 2*kMaxT + 1
+    HaloPlan plan[kMaxHaloDepth + 1] = {};               // by halo depth 1 .. max_depth
     int max_depth = 2;                                   // deepest plan built
     std::shared_ptr<LocalGroup<misor_grid>> local;       // in-process transport (local_group.h)
     bool overlap = true;            // exchange on cstream while the interior sweeps
@@ -185,6 +186,10 @@ inline double* pbuf(misor_grid* g, long long x) {
     const int b = (int)(x % g->np);
     return g->fld[b == 2 ? kP2 : kP0 + b];
 }
+// cell (0,0) of the field stored at base
+inline double* origin(const misor_grid* g, double* base) {
+    return base + (long long)kYOff * g->pitch + kXOff;
+}
 
 // ---- shared helpers (defined in the unit named beside each group) ----
 
@@ -216,9 +221,9 @@ MISOR_HIDDEN int grid_adopt(misor_grid* g, const double* p_dev, const double* rh
 
 // misor_comm.hip
 MISOR_HIDDEN int allreduce(misor_grid* g, double* dev, int n, int is_max, hipStream_t s = nullptr);
-MISOR_HIDDEN void build_plan(misor_grid* g, int d);
 MISOR_HIDDEN int collect_comm_times(misor_grid* g);
 MISOR_HIDDEN int exchange(misor_grid* g, double* field, int d, hipStream_t s = nullptr);
+MISOR_HIDDEN int gather(misor_grid* g, const double* field, double* host);
 MISOR_HIDDEN int p_halo(misor_grid* g);
 MISOR_HIDDEN int wait_stream(misor_grid* g, hipStream_t s);
 

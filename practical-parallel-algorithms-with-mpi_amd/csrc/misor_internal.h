@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <string>
 
+#include "decomp2.h"  // HaloPlan
 #include "misor.h"
 
 namespace misor {
@@ -362,17 +363,8 @@ hipError_t mg_tail_prepare();        // once per device before the first launch
 void launch_mg_tail(hipStream_t s, const MgTailLevel* levels, int count, MgTailState* st,
                     size_t lds);
 
-// 8-neighbour halo exchange of one field (halo.hip): regions in local cell
-// coordinates; direction order L, R, B, T, BL, BR, TL, TR
-constexpr int kDirs = 8;
-struct HaloRegion {
-    int x0, y0, w, h;  // first cell and extent (local reference indices)
-    long long off;     // offset in the packed buffer (doubles)
-};
-struct HaloPlan {
-    HaloRegion send[kDirs], recv[kDirs];
-    long long total;  // doubles in each of the send / recv buffers
-};
+// 8-neighbour halo exchange of one field (halo.hip) by a plan of decomp2.h
+static_assert(kMaxHaloDepth == 2 * kMaxT + 1, "decomp2.h: the deepest halo plan");
 void launch_pack(hipStream_t s, const double* field, long long pitch, const HaloPlan& plan,
                  double* sendbuf);
 void launch_unpack(hipStream_t s, double* field, long long pitch, const HaloPlan& plan,

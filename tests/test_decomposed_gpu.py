@@ -337,9 +337,7 @@ def test_pipelined_reserve(reserve):
     assert np.array_equal(got, want), np.argwhere(got != want)[:5]
 
 
-@pytest.mark.parametrize("world,dims", [(2, (0, 0)), (4, (0, 0)), (6, (3, 2)), (8, (0, 0))])
-@pytest.mark.parametrize("depth", [1, 2, 7])
-def test_exchange_rank_fill(world, dims, depth):
+def rank_fill(world, dims, ni, nj, depth, also=None):
     """the skeleton's printExchange check (assignment-5/skeleton/src/solver.c:38-66):
     every rank fills the cells it owns -- its interior plus the ghost cells on
     its physical sides -- with a code of (rank, global i, global j) and the
@@ -347,8 +345,7 @@ def test_exchange_rank_fill(world, dims, depth):
     every rank's (ni+2) x (nj+2) array holds the code its owner wrote for that
     global cell: own cells untouched, halo edges and corners from the 8
     neighbours (corner ghosts of a physical side from the neighbour that owns
-    them)"""
-    ni, nj = 61, 47
+    them).  also(g): a further check every rank makes on its grid afterwards"""
 
     def code(r, gi, gj):
         return r * 1e6 + gj * 1000.0 + gi
@@ -369,7 +366,10 @@ def test_exchange_rank_fill(world, dims, depth):
             a = np.where(mine, code(r, gi, gj), -1.0)
             g.upload(M.U, a)
             g.exchange(M.U, depth)
-            return loc, g.download(M.U)
+            got = g.download(M.U)
+            if also:
+                also(g)
+            return loc, got
 
     outs = run_ranks(world, rank_fn, dims)
     ext = [extent(o[0]) for o in outs]
@@ -381,6 +381,28 @@ def test_exchange_rank_fill(world, dims, depth):
                        if a0 <= gi <= a1 and b0 <= gj <= b1]
                 assert len(own) == 1, (gi, gj, own)
                 assert got[j, i] == code(own[0], gi, gj), (r, i, j, got[j, i], own[0])
+
+
+@pytest.mark.parametrize("world,dims", [(2, (0, 0)), (4, (0, 0)), (6, (3, 2)), (8, (0, 0))])
+@pytest.mark.parametrize("depth", [1, 2, 7])
+def test_exchange_rank_fill(world, dims, depth):
+    rank_fill(world, dims, 61, 47, depth)
+
+
+def test_exchange_rank_fill_deepest():
+    """the deepest plan there is, 2 * kMaxT + 1 = 21: 2 x 2 ranks on 44 x 46
+    have blocks of 22 and 23 cells"""
+    rank_fill(4, (2, 2), 44, 46, 21)
+
+
+def test_exchange_depth_limited_by_block():
+    """3 x 2 ranks on 17 x 11: the smallest block has 5 cells, so plans exist to
+    depth 5 -- which exchanges correctly -- and depth 6 is refused"""
+    def refused(g):
+        with pytest.raises(M.MisorError, match=r"exchange depth 6 outside 1\.\.5"):
+            g.exchange(M.U, 6)
+
+    rank_fill(6, (3, 2), 17, 11, 5, also=refused)
 
 
 @pytest.mark.parametrize("world", [2, 4, 8])

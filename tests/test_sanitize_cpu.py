@@ -2,7 +2,7 @@
 the reference's failure mode is fail-fast; here memory errors, leaks and UB
 in the CPU-side code are caught by a sanitized build).
 
-Four executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
+Five executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
 -fno-sanitize-recover=undefined):
   * bin/asan/host-check (practical-parallel-algorithms-with-mpi_amd/host/
     sanitize_main.c): the .par reader on every .par the tests use, the
@@ -14,6 +14,11 @@ Four executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
   * bin/asan/decomp3-check (host/decomp3_check.cc): the 3D decompositions
     (csrc/decomp3.h) -- process grids of 1..16 ranks, owned boxes and slab
     gather ranges marked cell by cell, the refused cases, mutual neighbours;
+  * bin/asan/decomp2-check (host/decomp2_check.cc): the 2D decomposition and
+    its halo plans (csrc/decomp2.h) -- the process grids of 1..64 ranks
+    against the recorded MPI_Dims_create table, owned blocks marked cell by
+    cell, the 8-neighbour tables, and every send / receive region of every
+    rank at every halo depth followed cell by cell to its peer's region;
   * oracle/_asan/oracle-check (oracle/sanitize_main.c): every oracle
     function on small ragged grids, with the reference's iteration KATs and
     multi-threaded == scalar bit identity.
@@ -59,6 +64,12 @@ def test_pass_plan_sanitized():
 def test_decomp3_sanitized():
     build(PKG)
     out = run([os.path.join(PKG, "bin", "asan", "decomp3-check")])
+    assert "all checks passed" in out
+
+
+def test_decomp2_sanitized():
+    build(PKG)
+    out = run([os.path.join(PKG, "bin", "asan", "decomp2-check")])
     assert "all checks passed" in out
 
 
