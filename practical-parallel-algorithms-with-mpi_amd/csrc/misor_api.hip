@@ -3,8 +3,8 @@
 // Poisson init, and gather's entry), tuning and statistics.  The decomposition
 // arithmetic is in decomp2.h, the solve loop in misor_solve.hip, the NS step in
 // misor_ns.hip, communication (gather's transport too) in misor_comm.hip,
-// launch plans in misor_plan.hip; their shared state is struct misor_grid
-// (misor_grid.h).
+// launch plans in tb_plan.h (their device side in misor_plan.hip); their
+// shared state is struct misor_grid (misor_grid.h).
 
 #include "misor_grid.h"
 
@@ -157,32 +157,10 @@ static int set_geometry(misor_grid* g) {
         sp.pow2 = sp.idx2 == sp.idy2 && mant == 0.5 && e >= 1;
     }
     if (configure_sweep(g, kDefaultSweepVariant, 0, 1) != MISOR_OK) return MISOR_ENOMEM;
-    {
-        // temporally blocked pass: same physics, its own geometry; every cell of
-        // a neighbour's 2T-deep halo is updated (identical arithmetic), only the
-        // physical sides are bounded
-        constexpr int kBig = 1 << 29;
-        SweepParams& tp = g->tp;
-        tp = sp;
-        tp.upd_lo_i = sp.ghost_left ? 1 : -kBig;
-        tp.upd_hi_i = sp.ghost_right ? L.ni : kBig;
-        tp.upd_lo_j = sp.ghost_bottom ? 1 : -kBig;
-        tp.upd_hi_j = sp.ghost_top ? L.nj : kBig;
-        // an interior block (overlapped pass) streams no halo cell of src
-        tp.int_lo_i = sp.ghost_left ? -kBig : 1;
-        tp.int_hi_i = sp.ghost_right ? kBig : L.ni;
-        tp.int_lo_j = sp.ghost_bottom ? -kBig : 1;
-        tp.int_hi_j = sp.ghost_top ? kBig : L.nj;
-    }
-    if (g->dist) {
-        // blocks whose footprint (rows j0-2..j1+1, columns c0-2..c_end+1) stays clear
-        // of the halo on neighbour sides AND of the 2-deep send region can sweep
-        // while the exchange is in flight
-        sp.int_lo_i = L.neighbours[0] >= 0 ? 3 : -1000000000;
-        sp.int_hi_i = L.neighbours[1] >= 0 ? L.ni - 2 : 2000000000;
-        sp.int_lo_j = L.neighbours[2] >= 0 ? 3 : -1000000000;
-        sp.int_hi_j = L.neighbours[3] >= 0 ? L.nj - 2 : 2000000000;
-    }
+    // the temporally blocked pass: the same physics, the bounds of tb_plan.h
+    g->tp = sp;
+    tb_bounds(g->tp);
+    if (g->dist) sweep_interior_bounds(sp);
     return MISOR_OK;
 }
 
@@ -347,7 +325,8 @@ int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
     CREATE_STEP(set_geometry(g));
     CREATE_STEP(alloc_state(g));
     if (g->dist) CREATE_STEP(comm_setup(g, proxy));
-    if (configure_tb(g, default_tsteps(g, kDefaultTbVariant), kDefaultTbVariant, 0) != MISOR_OK)
+    if (configure_tb(g, default_tsteps(tb_input(g), kDefaultTbVariant), kDefaultTbVariant, 0) !=
+        MISOR_OK)
         CREATE_FAIL(MISOR_ENOMEM, "%s", g_err.c_str());
     if (hipStreamSynchronize(g->stream) != hipSuccess)
         CREATE_FAIL(MISOR_EHIP, "hipStreamSynchronize failed");
@@ -610,8 +589,8 @@ int misor_set_tuning(misor_grid* g, int key, int value) {
         // to the default rule.  A rejected request changes nothing.
         const bool prev = g->tsteps_set;
         g->tsteps_set = value > 0;
-        const int rc = configure_tb(g, value > 0 ? value : default_tsteps(g, g->tp.variant),
-                                    g->tp.variant, g->tb_rows_req);
+        const int T = value > 0 ? value : default_tsteps(tb_input(g), g->tp.variant);
+        const int rc = configure_tb(g, T, g->tp.variant, g->tb_rows_req);
         if (rc) g->tsteps_set = prev;
         return rc;
     }
@@ -628,7 +607,8 @@ int misor_set_tuning(misor_grid* g, int key, int value) {
         // without an explicit T request the default rule re-picks T (chained
         // small blocks run T = 8, unchained ones T = 7)
         g->tb_chain = value < 0 ? -1 : value != 0;
-        return configure_tb(g, g->tsteps_set ? g->tsteps : default_tsteps(g, g->tp.variant),
+        return configure_tb(g,
+                            g->tsteps_set ? g->tsteps : default_tsteps(tb_input(g), g->tp.variant),
                             g->tp.variant, g->tb_rows_req);
     case MISOR_TUNE_NS_FUSE: g->ns_fuse = value != 0; return MISOR_OK;
     case MISOR_TUNE_FINISH2: g->finish2 = value != 0; return MISOR_OK;
@@ -689,7 +669,7 @@ int misor_get_tuning(const misor_grid* g, int key, int* value) {
     case MISOR_TUNE_TB_VARIANT: *value = g->tp.variant; return MISOR_OK;
     case MISOR_TUNE_TB_ROWS: *value = g->tp.rows_per_block; return MISOR_OK;
     case MISOR_TUNE_TB_PERSISTENT: *value = g->tb_persistent; return MISOR_OK;
-    case MISOR_TUNE_TB_CHAIN: *value = chain_on(g, g->tp.variant); return MISOR_OK;
+    case MISOR_TUNE_TB_CHAIN: *value = chain_on(tb_input(g), g->tp.variant); return MISOR_OK;
     case MISOR_TUNE_NEAR_BAND: *value = g->near_exp; return MISOR_OK;
     case MISOR_TUNE_RES_LITE: *value = g->res_lite; return MISOR_OK;
     case MISOR_TUNE_EDGE_STEAL: *value = g->edge_steal; return MISOR_OK;

@@ -1,9 +1,10 @@
 // misor_grid.h -- the host-side state of a grid (struct misor_grid) and what
 // the C-ABI units share: misor_api.hip (errors, lifecycle, transfers, tuning,
 // statistics), misor_comm.hip (halo exchange, all-reduce and gather over RCCL
-// or the in-process transport), misor_plan.hip (launch geometry, chained-pass
-// plans), misor_solve.hip (the solve loop) and misor_ns.hip (the NS step).
-// The 2D decomposition and the halo plans are plain arithmetic in decomp2.h.
+// or the in-process transport), misor_plan.hip (the launch plans' buffers and
+// the upload of the chained-pass lists), misor_solve.hip (the solve loop) and
+// misor_ns.hip (the NS step).  The 2D decomposition and the halo plans are
+// plain arithmetic in decomp2.h, the launch plans in tb_plan.h.
 // Internal: nothing here is part of include/misor.h.
 #pragma once
 
@@ -227,20 +228,22 @@ MISOR_HIDDEN int gather(misor_grid* g, const double* field, double* host);
 MISOR_HIDDEN int p_halo(misor_grid* g);
 MISOR_HIDDEN int wait_stream(misor_grid* g, hipStream_t s);
 
+// what the launch plans (tb_plan.h) read off a grid
+inline TbInput tb_input(const misor_grid* g) {
+    return TbInput{g->loc.ni,   g->loc.nj,        g->dist,        g->desc.imax,
+                   g->desc.jmax, {g->loc.dims[0], g->loc.dims[1]}, g->max_depth,
+                   g->tb_chain, g->tb_persistent, g->tb_rows_req, g->tb_reserve,
+                   g->tsteps,   g->tsteps_set};
+}
+
 // misor_plan.hip
-MISOR_HIDDEN bool chain_on(const misor_grid* g, int variant);
 MISOR_HIDDEN int chain_plan(misor_grid* g, int variant, int Tp, int part,
                       const misor_grid::ChainPlan** out);
 MISOR_HIDDEN int configure_sweep(misor_grid* g, int variant, int rows, int remap);
 MISOR_HIDDEN int configure_tb(misor_grid* g, int T, int variant, int rows);
-MISOR_HIDDEN int default_tsteps(const misor_grid* g, int variant);
 MISOR_HIDDEN void drop_chain_plans(misor_grid* g);
-MISOR_HIDDEN int effective_tsteps(const misor_grid* g);
 MISOR_HIDDEN int ensure_partials(misor_grid* g, int n);
-MISOR_HIDDEN int pick_rows_per_block(int ni, int nj, int waves);
-MISOR_HIDDEN void tb_geometry(const misor_grid* g, int T, SweepParams& tp);
-MISOR_HIDDEN int tb_halo_depth(int T, int variant);
-MISOR_HIDDEN int tb_parts(const SweepParams& tp);
+MISOR_HIDDEN const TbResidency& tb_residency();
 
 // misor_solve.hip
 MISOR_HIDDEN bool lex_tiled_on(const misor_grid* g);

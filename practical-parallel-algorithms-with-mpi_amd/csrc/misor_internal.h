@@ -10,6 +10,7 @@
 
 #include "decomp2.h"  // HaloPlan
 #include "misor.h"
+#include "tb_plan.h"  // kMaxT, kStripCells, SweepParams, the launch plans
 
 namespace misor {
 
@@ -33,10 +34,7 @@ namespace misor {
 // Padding cells are zero and never feed an interior result.
 // ---------------------------------------------------------------------------
 constexpr int kXOff = 15;
-constexpr int kMaxT = 10;                // iterations per temporally blocked pass (max)
 constexpr int kYOff = 2 * kMaxT + 16;
-constexpr int kLanes = 64;                 // wavefront
-constexpr int kStripCells = 2 * kLanes;    // 128 columns per wave (2 per lane)
 constexpr int kMaxWavesX = 16;             // strips per sweep workgroup (max)
 constexpr int kMaxAhead = 3;               // rows a sweep keeps in flight (max)
 
@@ -60,75 +58,9 @@ constexpr int kNumSweepVariants = 15;
 constexpr int kDefaultSweepVariant = 7;  // 8 strips, 2 rows ahead, nt stores (tools/tune_sweep.py)
 int sweep_waves(int variant);
 
-// temporally blocked sweep (sor_tb.hip): the built variants by their public
-// number (id): strips per workgroup, rows in flight
-// (x-neighbour shifts through ds_bpermute instead of DPP measured 5% slower:
-// profiles/r02_tune_bperm.txt)
-// 128-column strips (2 columns per lane), 2 waves per SIMD.
-// skew: the split-ring march in two independent stage chains per step (sor_tbh.h
-// hrs_step); hr: the split rhs ring, registers + LDS (sor_tbh.h)
-// The other numbers below kNumTbVariants are retired -- measured slower and no
-// longer built (DESIGN.md section 4:
-// 1 / 3 eight / one strips per workgroup, 4 three rows in flight, 5 four
-// columns per lane at one wave per SIMD, 6-8 strips exchanging edge columns
-// through LDS, 9 the skewed register-ring march, 10/11 an LDS row queue, 12 the
-// unskewed split ring); configuring one fails (tb_max_t = 0).  The register-ring
-// kernels run T <= kMaxT2 (above that their rhs ring spills); the split ring
-// (13) runs T up to kMaxT.
-constexpr int kMaxT2 = 8;
-struct TbVariant {
-    int id, waves, ahead, max_t, skew, hr;
-};
-constexpr TbVariant kTbVariants[] = {
-    {0, 4, 2, kMaxT2, 0, 0}, {2, 2, 2, kMaxT2, 0, 0}, {13, 4, 2, kMaxT, 1, 1}};
-constexpr int kNumTbVariants = 14;
-constexpr int kHrTbVariant = 13;   // the skewed split ring (T = 1 unskewed)
-// the short plan of capped solves (misor_solve.hip short_plan_on, pass_plan.h)
-constexpr int kShortTbVariant = kHrTbVariant;
-constexpr int kShortT = 10;
-constexpr long long kShortDistCells = 1LL << 28;  // decomposed: local blocks at least this big
-constexpr long long kHrAllCells = 1LL << 26;      // chained blocks from here: every solve > 8
-// iterations per pass: 8 on large local blocks, 7 below kTsteps8Cells cells
-// (32768^2 0.744 vs 0.785 ms/iteration, profiles/r02_tune_t789.txt; one rank's
-// 8192 x 16384 block at 8 GPUs 0.118-0.122 at T = 7 vs 0.125 at T = 8,
-// profiles/r02_small_rows.txt, r02_tb_rows_t8.txt)
-constexpr int kDefaultTsteps = 8;
-constexpr int kSmallBlockTsteps = 7;
-constexpr long long kTsteps8Cells = 1LL << 28;
-constexpr int kDefaultTbVariant = 0;   // 4 strips, 2 rows in flight
-// block heights tried, tallest first (misor_plan.hip pick_tb_rows)
-constexpr int kTbRowLadder[] = {576, 384, 288, 192};
-constexpr int kTbRowLadderLen = 4;
-constexpr int kTbSmallRows = 32;       // short block rows the work order takes last ...
-constexpr int kTbSmallRounds = 2;      // ... about this many resident rounds of them
-constexpr int kTbReserve = 16;         // slots a pipelined interior launch leaves free
-int tb_waves(int variant);
-// the split rhs ring (sor_tbh.h): stages 0 .. K-1 read registers, the rest LDS;
-// both rings have S slots, S = max(2K + D, 2(T - K) + 1) rounded up to even.
-// K: as few register stages as the LDS allows -- S <= kHrMaxSlots rows of 1 KB
-// per wave (two workgroups of four waves: 144 KB of the CU's 160)
-constexpr int kHrMaxSlots = 18;
-// The skewed form (sk = 1) keeps one more row in each ring.
-__host__ __device__ constexpr int hr_cost(int T, int D, int k, int sk = 0) {
-    const int a = 2 * k + D + sk, b = 2 * (T - k) + 1 + sk;
-    const int s = a > b ? a : b;
-    return s + (s & 1);
-}
-__host__ __device__ constexpr int hr_k(int T, int D, int sk = 0) {
-    for (int k = 0; k <= T; ++k)
-        if (hr_cost(T, D, k, sk) <= kHrMaxSlots) return k;
-    return T;
-}
-__host__ __device__ constexpr int hr_slots(int T, int D, int sk = 0) {
-    return hr_cost(T, D, hr_k(T, D, sk), sk);
-}
-// rhs ring slots of the steady march: interior block heights are multiples of it
-int tb_ring_slots(int T, int variant);
-// workgroups of a persistent pass resident on the device at once
+// workgroups of a persistent pass resident on the device at once: the
+// occupancy query behind tb_plan.h TbResidency (sor_tb.hip)
 int tb_resident(int T, int variant);
-int tb_max_t(int variant);
-int tb_out_width(int T, int variant);           // owned columns of one wave's strip
-int tb_nbx(int ni, int T, int variant);         // block columns of a pass of T iterations
 
 // Solver state that lives on the device between launches.  Written only by
 // the finish kernel (one workgroup) and read by the next sweep launch.
@@ -148,91 +80,6 @@ struct DevState {
                         // then all-reduced)
 };
 
-struct SweepParams {
-    long long pitch;
-    int ni, nj;          // local interior size
-    int rows_per_block;  // H (temporally blocked: block rows 0 .. nby_big-1 are H tall)
-    int nby;             // temporally blocked: block rows; rows nby_big .. nby-2 are
-                         // h_small tall, the last one takes the rest (tb_geometry)
-    int nby_big, h_small;
-    int parity;          // (ioff + joff) & 1 : global colour of local cell (0,0)
-    int ghost_left, ghost_right, ghost_bottom, ghost_top;  // physical boundary -> Neumann copy
-    int red_lo_i, red_hi_i, red_lo_j, red_hi_j;  // cells whose red value is computed
-    int variant;         // index into kSweepVariants
-    int nbx, nblocks;    // launch geometry (logical blocks nbx x nby)
-    int xcd_remap;       // deal consecutive logical blocks to one XCD
-    int part;            // 0: all blocks, 1: interior blocks only, 2: boundary blocks only
-    int int_lo_i, int_hi_i, int_lo_j, int_hi_j;  // footprint bounds of an interior block
-    int upd_lo_i, upd_hi_i, upd_lo_j, upd_hi_j;  // temporally blocked: cells updated
-                                                 // (1..n on physical sides, all on
-                                                 // neighbour sides)
-    double idx2, idy2, coef;  // 1/dx^2, 1/dy^2, factor (RB) or omega*factor (RBA)
-    int pow2;                 // idx2 == idy2 == 2^m, m >= 0: the default TB kernel's P2 form
-    int reserve;              // persistent launch: leave this many workgroup slots free
-                              // (host only; the comm / edge streams' kernels run there)
-    // chained passes (sor_tb.h rb_tbc_kernel): vertical runs of blocks taken
-    // from the launch's segment list, with work stealing
-    int chain;                // 1: blocks are 4 ring lengths tall, runs chain them
-    int nseg0;                // segments of the launch's initial list
-    int seg_cap;              // dynamic segment slots (created by steals)
-    int chain_blocks;         // blocks in the launch (its part)
-    int chain_edge;           // the edge list (strips at a physical left / right side)
-    int lite;                 // the split ring's steady chunks count the residual of the
-                              // stages before the last one on one row in S (a lower
-                              // bound; misor_solve.hip kLite)
-    int chain_grid;           // edge list: its workgroups (the first of the launch)
-    int seg_run[9];           // XCD x takes the initial segments [seg_run[x], seg_run[x+1])
-    unsigned long long* trace;  // diagnostics (MISOR_CHAIN_TRACE): per block L, 3 words --
-                                // start and end (wall clock, 100 MHz), workgroup | run start
-    const unsigned long long* seg_tmpl;  // the initial list (device; copied per launch)
-    // the split ring's edge kernel: once its own list is done, its workgroups
-    // steal from the main list's work area (initialised before either kernel
-    // starts: no_init on the main launch); nullptr: no second list
-    int* alt_work = nullptr;
-    int alt_nseg0 = 0;
-    int no_init = 0;          // the work area is initialised already (misor_solve.hip)
-};
-
-// Chained passes: a segment word holds the next unclaimed block row (bits
-// 0..25), the end block row, exclusive (26..51), and the column (52..63).
-// Work area of a chained launch: int head[kChainHead] (0..7: per-XCD tickets
-// of the initial segments, 8: dynamic segments created), then the words.
-constexpr int kChainBits = 26;
-constexpr unsigned long long kChainMask = (1ull << kChainBits) - 1;
-constexpr int kChainHead = 16;
-constexpr int kChainSegCap = 4096;       // dynamic slots per launch
-constexpr int kChainRingsPerBlock = 4;   // block height of a chained pass, in ring lengths
-// the chained split-ring pass (sor_tbh.h rb_tbhc_kernel): blocks of 8 ring
-// lengths (144 rows at T = 10), a block of a column at a physical left / right
-// side costing ~2.5 others (its strip's kSteadyEdge chunks run ~1.8x a steady
-// strip's; profiles/r05_hrsweep2_*.txt)
-constexpr int kHrChainRingsPerBlock = 8;
-constexpr double kHrChainEdgeCost = 2.5;
-// the same on a decomposed rank's block (its passes split in two parts around
-// the halo exchange): 10 ring lengths (180 rows) and an edge-column block at 3
-// others -- wall ms per iteration of the pipelined loop, alternated on one box
-// (profiles/r05_rank_geometry_ab.txt): the 8-GPU rank block with physical
-// left + bottom sides 0.121 against 0.139 at 8 / 2.5, bottom only 0.125 vs
-// 0.127, the 4-GPU block 0.204 vs 0.230, the 2-GPU block unchanged (sweeps:
-// r05_edge_rings_ab*.txt; a single rank, without the split, stays at 144 rows)
-constexpr int kHrChainRingsDist = 10;
-constexpr double kHrChainEdgeCostDist = 3.0;
-// chained passes by default on local blocks below this many cells: there the
-// unchained blocks are short and their 4T warm-up rows cost most (one 8-GPU
-// rank's 8192 x 16384 of the 32768^2 bench: 0.106 vs 0.110-0.118 ms per
-// iteration); on larger blocks the unchained 576-row blocks are ahead
-// (32768^2: 0.661 vs 0.695-0.709; profiles/r03_chain_rows.txt)
-constexpr long long kChainCells = 1LL << 28;
-constexpr double kChainEdgeCost = 2.0;   // a block of a column at a physical left / right
-                                         // side, in steady blocks (segment lengths): a
-                                         // kSteadyEdge block measures ~1.5; the edge
-                                         // kernel's workgroups cannot steal from the main
-                                         // one's, so it is given a few more than its share
-                                         // (profiles/r03_chain_edge_cost.txt)
-__host__ __device__ inline unsigned long long chain_word(int col, int next, int end) {
-    return ((unsigned long long)col << (2 * kChainBits)) |
-           ((unsigned long long)end << kChainBits) | (unsigned long long)next;
-}
 // zero the head, copy the initial list, empty the dynamic slots
 void launch_chain_init(hipStream_t s, int* work, const unsigned long long* tmpl, int nseg0,
                        int cap);
@@ -369,7 +216,6 @@ void launch_pack(hipStream_t s, const double* field, long long pitch, const Halo
                  double* sendbuf);
 void launch_unpack(hipStream_t s, double* field, long long pitch, const HaloPlan& plan,
                    const double* recvbuf);
-int sweep_partials(int ni, int nj, int rows_per_block, int waves, int* nbx, int* nby);
 // in-process transport: out[k] = combination (sum / max, rank order) of
 // gather[q * kMaxT + k] over q < nranks, k < n
 void launch_local_combine(hipStream_t s, const double* gather, int nranks, int n, int is_max,

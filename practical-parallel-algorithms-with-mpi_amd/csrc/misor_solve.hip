@@ -141,7 +141,7 @@ static int exact_tail(misor_grid* g, int itermax, int it0, double res0, int* ite
     sp.part = 0;
     int it = it0, far = 0;
     double r = res0;
-    const int T = effective_tsteps(g);
+    const int T = effective_tsteps(tb_input(g), g->tp.variant);
     while ((r >= epssq) && (it < itermax)) {
         double* src = pbuf(g, g->cur);
         double* dst = pbuf(g, g->cur + 1);
@@ -234,7 +234,8 @@ static bool short_plan_on(const misor_grid* g, int todo) {
     const bool all = g->short_all || (g->short_all_lite && g->res_lite);
     // (decomposed: only where the smallest block holds the split ring's halo)
     const bool short_fits = !g->dist || tb_halo_depth(kShortT, kShortTbVariant) <= g->max_depth;
-    return g->short_plan && short_fits && effective_tsteps(g) == kDefaultTsteps &&
+    return g->short_plan && short_fits &&
+           effective_tsteps(tb_input(g), g->tp.variant) == kDefaultTsteps &&
            (all ? todo > kDefaultTsteps : short_plan_saves_passes(todo, kShortT, kDefaultTsteps));
 }
 
@@ -274,7 +275,7 @@ struct RbSolve {
     int nparts_of(int Tk) const {
         if (T == 1 || Tk == T) return nparts;
         SweepParams tp = tpl;
-        tb_geometry(g, Tk, tp);
+        tb_geometry(tb_input(g), tb_residency(), Tk, tp);
         return tb_parts(tp);
     }
     const double* src(long long k) const { return pbuf(g, cur0 + k); }
@@ -288,11 +289,11 @@ struct RbSolve {
 
 static RbSolve plan_solve(misor_grid* g, int todo, double cells) {
     const bool shortp = short_plan_on(g, todo);
-    const int T = shortp ? kShortT : effective_tsteps(g);
+    const int T = shortp ? kShortT : effective_tsteps(tb_input(g), g->tp.variant);
     SweepParams tpl = g->tp;  // the plan's geometry
     if (shortp) {
         tpl.variant = kShortTbVariant;
-        tb_geometry(g, T, tpl);
+        tb_geometry(tb_input(g), tb_residency(), T, tpl);
     }
     // halo of src each pass needs: 2T, one row more for the skewed split ring
     // (tb_halo_depth).  effective_tsteps and short_plan_on keep it within the
@@ -339,7 +340,7 @@ static int launch_chained(const RbSolve& c, hipStream_t s, int part, SweepParams
     SweepParams te = tp;
     use_chain_list(te, pl->edge);
     te.chain_edge = 1;
-    te.reserve = std::max(0, tb_resident(Tp, tp.variant) - eg);
+    te.reserve = std::max(0, tb_residency()(Tp, tp.variant) - eg);
     SweepParams tm = tp;
     use_chain_list(tm, pl->main);
     tm.chain_edge = 0;
@@ -412,7 +413,7 @@ static int launch_pass(const RbSolve& c, hipStream_t s, int part, const double* 
     // until the pass is over, so without them the exchange would only start
     // at the end of the interior blocks
     tp.reserve = part == 1 ? g->tb_reserve : 0;
-    if (Tp != c.T) tb_geometry(g, Tp, tp);  // narrower cone: wider strips
+    if (Tp != c.T) tb_geometry(tb_input(g), tb_residency(), Tp, tp);  // narrower cone: wider strips
     tp.lite = c.lite_pass(Tp, force) ? 1 : 0;
     if (tp.chain) return launch_chained(c, s, part, tp, src, dst, Tp, force, partials);
     // persistent work-queue launch on the grid stream (whole passes and

@@ -509,13 +509,6 @@ void launch_finish2(hipStream_t s, const double* partials, int nparts, int T, De
 
 int sweep_waves(int variant) { return kSweepVariants[variant].waves; }
 
-int sweep_partials(int ni, int nj, int rows_per_block, int waves, int* nbx, int* nby) {
-    const int strips = (ni + kStripCells - 1) / kStripCells;
-    *nbx = (strips + waves - 1) / waves;
-    *nby = (nj + rows_per_block - 1) / rows_per_block;
-    return (*nbx) * (*nby);
-}
-
 void launch_sweep(hipStream_t s, const SweepParams& prm, const double* src, double* dst,
                   const double* rhs, double* partials, const DevState* st) {
 #define SWEEP(W, D, NT, LNT)                                                                \

@@ -118,7 +118,7 @@ __device__ __forceinline__ double m2c(double a, double c) { return __builtin_fma
 // (a subnormal a + b is exact too) and rhs minus that exact product is one
 // fma -- the same bits with 2 of the 11 FP64 instructions of an update fewer.
 // Holds while |a| k and |b| k stay below DBL_MAX (|p| < ~1e298 at k = 2^30);
-// the host enables it only for such a spacing (misor_plan.hip configure_tb).
+// the host enables it only for such a spacing (misor_api.hip set_geometry).
 template <bool P2>
 __device__ __forceinline__ double resid(double rhs, double a, double b, double idx2, double idy2) {
     if (P2) return __builtin_fma(-(a + b), idx2, rhs);
@@ -683,7 +683,10 @@ __device__ __forceinline__ void tb_strip2(const SweepParams& prm, const double* 
 
 // block rows: nby_big of H = rows_per_block rows, then h_small-row ones
 // (short blocks, which the work order takes last), the last takes the rest
-// (misor_plan.hip tb_geometry)
+// (tb_plan.h tb_geometry).  tb_plan.h tb_block_rows is the host's copy of this
+// and tb_interior of tb_block's part test below: with both shared from that
+// header the code objects of the T <= 8 units came out different, so the
+// kernels keep theirs
 __device__ __forceinline__ void block_rows(const SweepParams& prm, int by, int& j0, int& j1) {
     const int H = prm.rows_per_block;
     j0 = by < prm.nby_big ? 1 + by * H : 1 + prm.nby_big * H + (by - prm.nby_big) * prm.h_small;
@@ -738,6 +741,7 @@ __device__ __forceinline__ void tb_block(const SweepParams& prm, const double* _
     int j0, j1;
     block_rows(prm, by, j0, j1);
     if (prm.part != 0) {  // overlapped decomposed pass: blocks clear of the halo first
+        // (the host's copy: tb_plan.h tb_interior)
         const int lo = 1 + bx * WAVES * OW - 2 * T;
         const int hi = 1 + (bx * WAVES + WAVES - 1) * OW - 2 * T + kStripCells - 1;
         const bool interior = lo >= prm.int_lo_i && hi <= prm.int_hi_i &&
@@ -833,7 +837,7 @@ __device__ __forceinline__ void for_each_block(const SweepParams& prm, int* __re
 // Work: segments = ranges of block rows of one column, one 64-bit word each
 // (chain_word): the next unclaimed block row N, the end E (exclusive), the
 // column.  A launch starts from a host-built list of segments (about one per
-// resident workgroup, misor_plan.hip chain_plan), in one run per XCD (the
+// resident workgroup, tb_plan.h chain_lists), in one run per XCD (the
 // slow blocks first; neighbouring columns on one XCD share its L2: the
 // strips' overlapping columns).  A workgroup takes a segment by ticket and
 // claims its blocks one by one
@@ -858,7 +862,7 @@ __device__ __forceinline__ void for_each_block(const SweepParams& prm, int* __re
 // ---------------------------------------------------------------------------
 // a block row [j0, j1) that can be part of a run: its cone clear of the
 // physical bottom / top sides and a height the static ring divides
-// (tb_strip2's rows_in); misor_plan.hip chain_plan uses the same test
+// (tb_strip2's rows_in); tb_plan.h tb_steady_row is the host's copy
 template <int T, int D>
 __host__ __device__ inline bool chain_rows_ok(const SweepParams& prm, int j0, int j1) {
     constexpr int S = ring_slots<T, D>();
@@ -1251,7 +1255,7 @@ __device__ __forceinline__ void chain_run(const SweepParams& prm, const double* 
 }
 
 // chained persistent pass (2-column strips); work = the launch's work area
-// (int head[kChainHead], then the segment words; misor_plan.hip chain_plan)
+// (int head[kChainHead], then the segment words; tb_plan.h chain_lists)
 template <int T, int WAVES, int D, bool P2, int EDGE = 0>
 __global__ __launch_bounds__(kLanes* WAVES, 2) void rb_tbc_kernel(
     SweepParams prm, const double* __restrict__ src, double* __restrict__ dst,

@@ -1,5 +1,5 @@
-// sor_tb.hip -- host side of the temporally blocked sweep: strip geometry and
-// the launch dispatch over T (each T's kernels are instantiated in its own
+// sor_tb.hip -- host side of the temporally blocked sweep: the launch and
+// occupancy dispatch over T (each T's kernels are instantiated in its own
 // unit, sor_tb_inst.hip compiled with MISOR_TB_T = T, so the build runs in
 // parallel).  Device code: sor_tb.h.
 #include <algorithm>
@@ -7,33 +7,6 @@
 #include "misor_internal.h"
 
 namespace misor {
-
-// the built variant of that public number; a retired one: max_t = 0
-static const TbVariant& tb_variant(int variant) {
-    static constexpr TbVariant retired = {-1, 4, 2, 0, 0, 0};
-    for (const TbVariant& v : kTbVariants)
-        if (v.id == variant) return v;
-    return retired;
-}
-
-int tb_max_t(int variant) { return tb_variant(variant).max_t; }
-
-int tb_out_width(int T, int /*variant*/) { return kStripCells - 4 * T; }
-
-int tb_waves(int variant) { return tb_variant(variant).waves; }
-
-int tb_ring_slots(int T, int variant) {
-    const TbVariant& v = tb_variant(variant);
-    if (v.hr) return hr_slots(T, v.ahead, v.skew && T >= 2 ? 1 : 0);
-    return 2 * T + v.ahead + (v.ahead & 1);  // sor_tb.h ring_slots
-}
-
-int tb_nbx(int ni, int T, int variant) {
-    const int ow = tb_out_width(T, variant);
-    const int strips = (ni + ow - 1) / ow;
-    const int waves = tb_waves(variant);
-    return (strips + waves - 1) / waves;
-}
 
 __global__ void chain_init_kernel(int* work, const unsigned long long* tmpl, int nseg0,
                                   int cap) {

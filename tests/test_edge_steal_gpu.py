@@ -16,7 +16,7 @@ included, and res is bit-equal among EDGE_STEAL 0, 1 and 2.
 Shapes.  Blocks are one ring length tall (MISOR_TUNE_TB_ROWS = S: 6, 12, 18
 rows at T = 2, 5, 10) and 4 strips of 128 - 4T columns wide; 4 block columns,
 the first and the last of them edge columns (a strip at a physical left /
-right side), the two between them the main list's.  misor_plan.hip chain_plan
+right side), the two between them the main list's.  tb_plan.h chain_lists
 cuts a column's steady run into segments of cost / G blocks, G the resident
 workgroups: cost = 1 per main block, 2.5 per edge-column block, 2.5 (S + 4T) /
 S per block whose cone reaches the bottom / top side (those are segments of
@@ -60,7 +60,7 @@ def ring(T):
 
 def geometry(ni, nj, T):
     """block columns and rows of a pass of T iterations with blocks of one ring
-    length; per column: an edge column? (misor_plan.hip chain_plan edge_col);
+    length; per column: an edge column? (tb_plan.h tb_edge_col);
     per block row: steady-able? (sor_tbh.h hr_chain_rows_ok, one rank)"""
     S, OW = ring(T), 128 - 4 * T
     nbx = -(-(-(-ni // OW)) // W)

@@ -242,7 +242,7 @@ def test_decomposed_leading_stage_near_eps():
 # The smallest decomposed block: two ranks whose local side across the split is
 # exactly 2T for the requested T.  The skewed split ring exchanges a 2T + 1-deep
 # halo, which such a block cannot hold, so the library runs T - 1 iterations a
-# pass there (misor_plan.hip effective_tsteps); with a 2T-deep halo its leading
+# pass there (tb_plan.h effective_tsteps); with a 2T-deep halo its leading
 # stages would count a stale row into their residuals.
 SMALLEST = [(T, dims) for T in (3, 4, 10) for dims in ((1, 2), (2, 1))]
 # ten consecutive iterations from the second pass on: every stage of a pass of

@@ -2,7 +2,7 @@
 the reference's failure mode is fail-fast; here memory errors, leaks and UB
 in the CPU-side code are caught by a sanitized build).
 
-Five executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
+Six executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
 -fno-sanitize-recover=undefined):
   * bin/asan/host-check (practical-parallel-algorithms-with-mpi_amd/host/
     sanitize_main.c): the .par reader on every .par the tests use, the
@@ -19,6 +19,13 @@ Five executables, built by `make asan` (gcc / g++ -fsanitize=address,undefined
     against the recorded MPI_Dims_create table, owned blocks marked cell by
     cell, the 8-neighbour tables, and every send / receive region of every
     rank at every halo depth followed cell by cell to its peer's region;
+  * bin/asan/tb-plan-check (host/tb_plan_check.cc): the launch plans of the
+    temporally blocked pass (csrc/tb_plan.h) -- over ragged and tall shapes,
+    every pass length of every built variant, requested block heights,
+    chaining, physical sides and resident counts: the block rows of every
+    geometry tile the rows, the segment lists of every part hold each of its
+    blocks once, and the table recorded before the arithmetic moved to the
+    header (tests/golden/tb_plan_parent.txt) comes out again;
   * oracle/_asan/oracle-check (oracle/sanitize_main.c): every oracle
     function on small ragged grids, with the reference's iteration KATs and
     multi-threaded == scalar bit identity.
@@ -70,6 +77,13 @@ def test_decomp3_sanitized():
 def test_decomp2_sanitized():
     build(PKG)
     out = run([os.path.join(PKG, "bin", "asan", "decomp2-check")])
+    assert "all checks passed" in out
+
+
+def test_tb_plan_sanitized():
+    build(PKG)
+    out = run([os.path.join(PKG, "bin", "asan", "tb-plan-check"),
+               os.path.join(ROOT, "tests", "golden", "tb_plan_parent.txt")])
     assert "all checks passed" in out
 
 
