@@ -170,6 +170,26 @@ def test_solve_fixed_iterations_bitwise(golden, dims, itermax, tune):
         assert res == pytest.approx(res_ref, rel=1e-12)
 
 
+@pytest.mark.parametrize("dims", [(32, 16, 16), (96, 48, 16), (33, 17, 17)])
+def test_resident_barrier_groups_bitwise(golden, dims):
+    """the resident solve's two-level barrier where its per-group arrival count
+    (nb - x + 7) / 8 and its target n * min(nb, 8) differ from a count of all
+    workgroups: one full box (one group of one), nine full boxes (group 0 has
+    two members, groups 1-7 one each) and eight ragged boxes, seven of them
+    nearly empty"""
+    prm = params(golden, "a6_dcavity.par", imax=dims[0], jmax=dims[1], kmax=dims[2],
+                 eps=1e-150, itermax=6)
+    shape = (dims[2] + 2, dims[1] + 2, dims[0] + 2)
+    st = random_state(shape, sum(dims))
+    ns, g = pair(prm, st, 0.02, EPILOGUE_PATHS["resident"])
+    with g:
+        it_ref, res_ref = ns.solve()
+        it, res = g.solve()
+        assert it == it_ref == 6
+        assert_fields_equal(ns, g, "solve")  # p incl. every ghost, and nothing else touched
+        assert res == pytest.approx(res_ref, rel=1e-12)
+
+
 @pytest.mark.parametrize("tune", SOLVE_TUNES)
 @pytest.mark.parametrize("dims,eps", [((24, 20, 16), 1e-3), ((40, 12, 10), 1e-4),
                                       ((33, 33, 33), 1e-4), ((64, 32, 32), 1e-4)])
