@@ -19,6 +19,16 @@ Fixtures:
   ns3d_dcavity_short.npz / ns3d_canal_short.npz  the reference's 3D NS (assignment-6/src,
                            oracle/_ref/libref3d.so) on its dcavity/canal .par at reduced
                            grids, 16 time steps: per-step iterations, p, u, v, w, t
+  ns3d_force_short.npz     the reference's 3D NS on a6_dcavity.par with gx 0.5, gy -1.0,
+                           gz 0.25, gamma 0.7, re 50 at 16x12x10, tau -1 and dt 0.005 (the
+                           fixed-dt branch of its main loop), 12 steps: per-step iterations,
+                           p, u, v, w, t, and the te at which the run is these 12 steps
+  ns_force_short.npz       composed RB-NS on a6_dcavity.par with gx 0.5, gy -1.0, gamma 0.7,
+                           re 50 at 48x32, tau 0.5, 40 steps: per-step iterations, p, u, v,
+                           t, and the te at which the run is these 40 steps
+                           (both: overrides of tests/ns_param_sets.py written to a temporary
+                           .par; the generator asserts the run stays finite and that at
+                           least half of its steps converge below itermax)
   ns_seq_dcavity_lex_100.npz    the same run to te=0.0125 (100 steps): p, u, v, t
   ns_seq_dcavity_lex_short.npz  the reference's own NS (assignment-5/sequential, its
                            lexicographic `solve`) on its dcavity.par, te=0.05: p, u, v,
@@ -85,10 +95,61 @@ def ns3d_fixtures():
         print(out, n, "steps", int(iters.sum()), "iterations")
 
 
+def force_fixtures():
+    """whole runs off the shipped files' physical parameters
+    (tests/ns_param_sets.py FORCE_RUN_*): forces on every axis, gamma 0.7,
+    re 50, on a6_dcavity.par written with these overrides to a temporary file"""
+    import pathlib
+    import tempfile
+
+    import ns_param_sets as PS
+    import orc3
+    assert orc3.have_ref3(), "build oracle/_ref first: make -C oracle ref"
+
+    def check(n, steps, iters, itermax, fields):
+        assert n == steps, (n, steps)
+        assert all(np.isfinite(a).all() for a in fields), "the run does not stay finite"
+        conv = int((iters < itermax).sum())
+        assert 2 * conv >= n, "only %d of %d steps converge below itermax" % (conv, n)
+        return conv
+
+    with tempfile.TemporaryDirectory() as d:
+        tmp = pathlib.Path(d)
+        # 3D, tau -1: the fixed-dt branch of the main loop (assignment-6/src/main.c:46)
+        steps = PS.FORCE_RUN_3D_STEPS
+        path = PS.write_par(HERE, tmp, "a6_dcavity.par", **PS.FORCE_RUN_3D)
+        prm = orc3.read_par3(path)
+        n, iters, p, u, v, w, t = orc3.ref3_run(path, max_steps=steps)
+        conv = check(n, steps, iters, prm["itermax"], (p, u, v, w))
+        te = t - 0.5 * prm["dt"]  # the run to te is these steps
+        n_te, iters_te, p_te = orc3.ref3_run(path, te=te)[:3]
+        assert n_te == steps and np.array_equal(iters_te, iters) and np.array_equal(p_te, p)
+        dims = tuple(prm[k] for k in ("imax", "jmax", "kmax"))
+        np.savez_compressed(os.path.join(HERE, "ns3d_force_short.npz"), steps=n, iters=iters,
+                            p=p, u=u, v=v, w=w, t=t, te=te, dims=np.array(dims))
+        print("ns3d_force_short.npz", n, "steps", int(iters.sum()), "iterations,", conv,
+              "steps converged")
+        # 2D, tau 0.5 (composed RB-NS as the other ns_*_rb fixtures)
+        steps = PS.FORCE_RUN_2D_STEPS
+        path = PS.write_par(HERE, tmp, "a6_dcavity.par", **PS.FORCE_RUN_2D)
+        prm = orc.read_par(path)
+        n, iters, p, u, v, t = orc.ref_ns(path, max_steps=steps, solver=1)
+        conv = check(n, steps, iters, prm["itermax"], (p, u, v))
+        t_before = orc.ref_ns(path, max_steps=steps - 1, solver=1)[5]
+        te = 0.5 * (t_before + t)  # the run to te is these steps
+        n_te, iters_te, p_te = orc.ref_ns(path, te=te, solver=1)[:3]
+        assert n_te == steps and np.array_equal(iters_te, iters) and np.array_equal(p_te, p)
+        np.savez_compressed(os.path.join(HERE, "ns_force_short.npz"), steps=n, iters=iters, p=p,
+                            u=u, v=v, t=t, te=te)
+        print("ns_force_short.npz", n, "steps", int(iters.sum()), "sweeps,", conv,
+              "steps converged")
+
+
 def main(full=True):
     assert orc.have_ref(), "build oracle/_ref first: make -C oracle ref"
     lex_fixtures()
     ns3d_fixtures()
+    force_fixtures()
 
     # reference data fixtures
     shutil.copyfile(os.path.join(REF, "assignment-4/p.dat"), os.path.join(HERE, "a4_p.dat"))
@@ -144,5 +205,7 @@ if __name__ == "__main__":
         lex_fixtures()
     elif "--3d-only" in sys.argv:
         ns3d_fixtures()
+    elif "--force-only" in sys.argv:
+        force_fixtures()
     else:
         main(full="--short" not in sys.argv)

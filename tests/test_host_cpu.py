@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+import ns_param_sets as PS
 import orc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,6 +119,19 @@ def test_reader_known_values(golden):
     assert float(d["xlength"]) == 30.0 and int(d["bcLeft"]) == 3 and int(d["itermax"]) == 500
     d = dump(os.path.join(golden, "a4_poisson.par"), poisson=True)
     assert float(d["omg"]) == 1.9 and int(d["itermax"]) == 1000000 and float(d["eps"]) == 1e-6
+
+
+def test_reader_reads_gz(golden, tmp_path):
+    """gz is a key of the 3D solver alone (assignment-6/src/parameter.c:77), so
+    the comparison with the 2D reference reader above never sees it"""
+    assert float(dump(os.path.join(golden, "a6_canal.par"))["gz"]) == 0.0
+    d = dump(PS.write_par(golden, tmp_path, "a6_dcavity.par", **PS.FORCE_RUN_3D))
+    assert (float(d["gx"]), float(d["gy"]), float(d["gz"])) == (0.5, -1.0, 0.25)
+    assert (float(d["gamma"]), float(d["re"]), float(d["tau"]), float(d["dt"])) == \
+        (0.7, 50.0, -1.0, 0.005)
+    assert (int(d["imax"]), int(d["jmax"])) == (16, 12)
+    d = dump(PS.write_par(golden, tmp_path, "a6_canal.par", gz=-3.3))
+    assert float(d["gz"]) == -3.3 and float(d["gx"]) == 0.0 and float(d["gy"]) == 0.0
 
 
 COMM_FILE = os.path.join(ROOT, "practical-parallel-algorithms-with-mpi_amd", "bin", "comm-file")

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import ns_param_sets as PS
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,6 +47,30 @@ def test_exe_ns_dcavity(golden, tmp_path):
     # pressure.dat: "%.2f %.2f %f" per interior cell, blank line after each row
     pr = np.loadtxt(tmp_path / "pressure.dat")
     assert pr.shape == (128 * 128, 3)
+    assert np.abs(pr[:, 2] - z["p"][1:-1, 1:-1].ravel()).max() <= 1e-6
+    ve = np.loadtxt(tmp_path / "velocity.dat")
+    u, v = z["u"], z["v"]
+    uc = ((u[1:-1, 1:-1] + u[1:-1, :-2]) / 2.0).ravel()
+    vc = ((v[1:-1, 1:-1] + v[:-2, 1:-1]) / 2.0).ravel()
+    assert np.abs(ve[:, 2] - uc).max() <= 1e-6
+    assert np.abs(ve[:, 3] - vc).max() <= 1e-6
+
+
+def test_exe_ns_forces(golden, tmp_path):
+    """gx 0.5, gy -1.0, gamma 0.7, re 50 on the cavity at 48 x 32 (from the .par
+    through solver_ns.c to misor_ns_desc): the 40 steps of the reference's own
+    run, tests/golden/ns_force_short.npz"""
+    z = np.load(os.path.join(golden, "ns_force_short.npz"))
+    PS.write_par(golden, tmp_path, "a6_dcavity.par", **dict(PS.FORCE_RUN_2D, te=float(z["te"])))
+    env = dict(os.environ, MISOR_ITERLOG=str(tmp_path / "iters.log"))
+    out = subprocess.run([os.path.join(BIN, "exe-ns"), "dcavity.par"], cwd=tmp_path, env=env,
+                         capture_output=True, text=True, timeout=300, check=True).stdout
+    assert "Parameters for dcavity" in out and "Solution took" in out
+    log = np.loadtxt(tmp_path / "iters.log")
+    assert len(log) == int(z["steps"]) == PS.FORCE_RUN_2D_STEPS
+    assert np.array_equal(log[:, 3].astype(int), z["iters"])
+    pr = np.loadtxt(tmp_path / "pressure.dat")
+    assert pr.shape == (48 * 32, 3)
     assert np.abs(pr[:, 2] - z["p"][1:-1, 1:-1].ravel()).max() <= 1e-6
     ve = np.loadtxt(tmp_path / "velocity.dat")
     u, v = z["u"], z["v"]

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import ns_param_sets as PS
 import orc3
 
 pytestmark = pytest.mark.gpu
@@ -54,12 +55,19 @@ def run_exe(par, tmp_path, **env):
 @pytest.mark.parametrize("name,over", [
     ("a6_dcavity.par", dict(imax=24, jmax=20, kmax=16, te=0.3)),
     ("a6_canal.par", dict(imax=40, jmax=12, kmax=10, te=0.6)),
+    # forces on every axis, gamma 0.7, re 50, tau -1: gz from the .par through
+    # solver_ns3d.c to misor3_desc, and the fixed-dt branch of the main loop
+    # (12 steps of dt 0.005: the run of tests/golden/ns3d_force_short.npz)
+    ("a6_dcavity.par", dict(PS.FORCE_RUN_3D, te=0.0575)),
 ])
 def test_exe_ns3d_matches_oracle(golden, tmp_path, name, over):
     par = write_par(golden, tmp_path, name, **over)
     prm = orc3.read_par3(str(par))
     ns = orc3.NS3(prm)
     n, iters, _ = ns.run()
+    if "gz" in over:
+        assert (prm["gx"], prm["gy"], prm["gz"], prm["tau"]) == (0.5, -1.0, 0.25, -1.0)
+        assert n == PS.FORCE_RUN_3D_STEPS
     out = run_exe(par, tmp_path)
     problem = prm["name"]
     assert "Parameters for %s" % problem in out

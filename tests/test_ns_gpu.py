@@ -184,11 +184,12 @@ def test_timestep_and_normalize(golden):
     g.close()
 
 
-def check_run(golden, fixture, parname, nranks=1, max_steps=-1):
+def check_run(golden, fixture, parname, nranks=1, max_steps=-1, over=None):
     """the run to the fixture's te against the fixture; max_steps > 0: only
-    the first max_steps steps, their iteration counts against the fixture's"""
+    the first max_steps steps, their iteration counts against the fixture's;
+    over: the parameters the fixture's run changed in the .par"""
     z = np.load(os.path.join(golden, fixture))
-    prm = par(golden, parname, te=float(z["te"]))
+    prm = par(golden, parname, **dict(over or {}, te=float(z["te"])))
     if nranks == 1:
         g = D.ns_grid(prm)
         steps, iters, t = D.run(g, prm, max_steps)

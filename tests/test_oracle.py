@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import ns_param_sets as PS
 import orc
 
 A6_DCAVITY = "a6_dcavity.par"
@@ -152,6 +153,50 @@ def test_ns_step_functions_vs_reference_bc_variants(golden, tmp_path):
         ns.run(solver=1, max_steps=6)
         for fld, ref in (("p", p), ("u", u), ("v", v)):
             assert np.array_equal(getattr(ns, fld), ref), (combo, fld)
+
+
+@needs_ref
+@pytest.mark.parametrize("tau,dt,steps", [(-1.0, PS.DTS[0], 6), (-1.0, PS.DTS[1], 2),
+                                          (0.5, 0.02, 6)])
+@pytest.mark.parametrize("set_id", PS.SET_IDS)
+@pytest.mark.parametrize("name", [A6_DCAVITY, A6_CANAL])
+def test_ns_step_functions_vs_reference_param_sets(golden, tmp_path, name, set_id, tau, dt, steps):
+    """the step functions off the shipped files' physical parameters
+    (tests/ns_param_sets.py: non-zero gx and gy, gamma 0 / 1 / 0.37, another re
+    and box), with both fixed dt values and with the adaptive dt: the 2D
+    reference is driven as whole steps, so a few steps at 40 x 20, bit for bit"""
+    over = dict(PS.overrides(set_id, ndim=2), imax=40, jmax=20, bcLeft=2, bcRight=3, bcBottom=1,
+                bcTop=2, tau=tau, dt=dt)
+    path = PS.write_par(golden, tmp_path, name, **over)
+    prm = orc.read_par(path)
+    for k, v in over.items():
+        assert prm[k] == v, k  # the override reached the file the reference reads
+    n, iters, p, u, v, t = orc.ref_ns(path, max_steps=steps, solver=1)
+    ns = orc.NS(prm)
+    n2, iters2, t2 = ns.run(solver=1, max_steps=steps)
+    assert n == n2 == steps and t == t2
+    assert np.array_equal(iters, iters2)
+    for fld, ref in (("p", p), ("u", u), ("v", v)):
+        assert np.isfinite(ref).all(), fld
+        assert np.array_equal(getattr(ns, fld), ref), (set_id, fld)
+
+
+@needs_ref
+def test_ns_force_run_vs_reference(golden, tmp_path):
+    """the run of tests/golden/ns_force_short.npz (forces, gamma 0.7, re 50 on
+    the cavity at 48 x 32, adaptive dt): oracle, reference and fixture agree"""
+    path = PS.write_par(golden, tmp_path, A6_DCAVITY, **PS.FORCE_RUN_2D)
+    steps = PS.FORCE_RUN_2D_STEPS
+    n, iters, p, u, v, t = orc.ref_ns(path, max_steps=steps, solver=1)
+    ns = orc.NS(orc.read_par(path))
+    n2, iters2, t2 = ns.run(solver=1, max_steps=steps)
+    assert n == n2 == steps and t == t2
+    z = np.load(os.path.join(golden, "ns_force_short.npz"))
+    assert np.array_equal(iters, iters2) and np.array_equal(iters, z["iters"])
+    assert t == float(z["t"])
+    for fld, ref in (("p", p), ("u", u), ("v", v)):
+        assert np.array_equal(getattr(ns, fld), ref), fld
+        assert np.array_equal(z[fld], ref), fld
 
 
 def test_lex_ns_oracle_vs_reference_fixture(golden):
