@@ -149,6 +149,13 @@ typedef struct {
     long long mg_tail_launches;
     long long mg_tail_fallbacks;
     double mg_tail_ms;
+    /* the last multigrid solve of this grid: the levels misor_solve_mg_dist kept
+     * distributed over the ranks (misor_mg_dist_levels' ndist); 0 after
+     * misor_solve_mg and on a grid that is not decomposed.  After
+     * misor_solve_mg_dist on a decomposed grid mg_tail_levels counts the fused
+     * levels of the gathered part, and the tail's other counters stay as they
+     * were */
+    int mg_dist_levels;
 } misor_stats;
 
 const char* misor_last_error(void);
@@ -235,7 +242,8 @@ int misor_solve_lex(misor_grid* g, int xorder, int* iters, double* res);
  * Geometric multigrid V-cycles for the same problem (lap p = rhs, Neumann by
  * ghost copy), cell-centred, with the red-black iteration of misor_solve_rb as
  * smoother and as coarsest-level solver (DESIGN.md "Geometric multigrid" has
- * the full definition).  Single rank only in this version, variant RB only.
+ * the full definition).  misor_solve_mg is the single-rank form, misor_solve_mg_dist
+ * below it cycles a decomposed grid; variant RB only.
  *
  * Levels: level 0 is the grid; level l+1 has (imax/2, jmax/2) cells of
  * (2dx, 2dy).  Coarsening stops at the first level with an odd side, a side
@@ -297,6 +305,46 @@ int misor_mg_tail(int imax, int jmax, int coarse_cells, int* first, int* count);
  * coarse_cells, itermax_coarse, maxcycles, a null grid, variant RBA; then
  * MISOR_ESTATE for a decomposed grid */
 int misor_solve_mg(misor_grid* g, const misor_mg_params* prm, int* cycles, double* res);
+
+/* The same cycle on a decomposed grid: collective over the ranks of g; with one
+ * rank (a grid that is not decomposed) it is misor_solve_mg.  Levels, smoothing,
+ * residual, restriction, interpolation weights, ghost copy, res and the loop
+ * over the cycles are those defined above, and p is bit for bit the
+ * single-rank misor_solve_mg's on every partition.
+ *
+ * The first levels of the hierarchy stay distributed: level 0 always; level
+ * l >= 1 iff level l-1 is, every rank's block of level l-1 has even sides, the
+ * halved blocks have both sides >= 4 and more than gather_cells cells
+ * (gather_cells < 0: the default, 65536), and level l is the coarsest level or
+ * has even block sides again.  A distributed level is a decomposed grid on the
+ * same process grid (the halved blocks are misor_decompose of the halved
+ * grid), smoothed -- or, as the coarsest level, solved -- by the decomposed
+ * red-black iteration.  The remaining levels are gathered: every rank holds
+ * them whole.  At the hand-over the ranks' restricted blocks are all-gathered
+ * into the whole-domain rhs and every rank runs the single-rank cycle on the
+ * gathered levels redundantly (the same bits everywhere, nothing is sent
+ * back); the correction reads the rank's window of the whole-domain e.
+ *
+ * res is level 0's all-reduced residual as misor_solve_rb_n returns it on a
+ * decomposed grid, the same bits on every rank, so all ranks run the same
+ * number of cycles.  It can differ from the single-rank res in its last bits,
+ * as misor_solve_rb's does outside the near band (MISOR_TUNE_NEAR_BAND): the
+ * cycle count is the single-rank one except where res lands within those bits
+ * of eps^2.
+ *
+ * Found before any device or collective call, by every rank from the same
+ * arithmetic: misor_solve_mg's MISOR_EINVAL cases in its order; then
+ * MISOR_ESTATE for a hierarchy of two or more levels on level-0 blocks with an
+ * odd side.  A later misor_solve_rb of the grid is unaffected. */
+int misor_solve_mg_dist(misor_grid* g, const misor_mg_params* prm, int gather_cells,
+                        int* cycles, double* res);
+/* host-only: how misor_solve_mg_dist splits the hierarchy of an imax x jmax grid
+ * over nranks (dims_in as misor_decompose): *nlevels = misor_mg_levels' count,
+ * the first *ndist of them distributed.  MISOR_EINVAL: misor_decompose's and
+ * misor_mg_levels' cases, a null nlevels or ndist; MISOR_ESTATE: the refusal
+ * above.  The outputs are untouched on an error. */
+int misor_mg_dist_levels(int nranks, const int dims_in[2], int imax, int jmax,
+                         int coarse_cells, int gather_cells, int* nlevels, int* ndist);
 
 /* NS step kernels (assignment-5/sequential/src/solver.c) */
 int misor_ns_setup(misor_grid* g, const misor_ns_desc* ns);

@@ -126,7 +126,130 @@ __global__ __launch_bounds__(kMgTileW) void mg_prolong_correct_kernel(
     }
 }
 
+// The same correction on one rank's block of a decomposed level
+// (misor_solve_mg_dist): p is the block, e the coarse array seen from the
+// block -- e + e_off is its cell (0, 0), which is the coarse block's own array
+// (e_off 0, its halo exchanged 1 deep, corners included) or the block's window
+// of a whole-domain level.  phys has bit 0 / 1 / 2 / 3 set where the block's
+// left / right / bottom / top side is the domain's: there the neighbour index
+// is clamped as above and the side's ghost copy of p is written; on a side
+// that borders another rank the coarse halo cell is read and no ghost is
+// written (the neighbour owns that cell of p).  e_off 0 with phys 15 is
+// mg_prolong_correct_kernel, expression for expression.
+__global__ __launch_bounds__(kMgTileW) void mg_prolong_correct_dist_kernel(
+    double* __restrict__ p, const double* __restrict__ e, long long e_off, int phys, int nic,
+    int njc, long long pitch, long long pitch_c) {
+    const int I = blockIdx.x * kMgTileW + threadIdx.x + 1;
+    if (I > nic) return;
+    const int J0 = blockIdx.y * kMgTileH + 1;
+    const int J1 = min(J0 + kMgTileH - 1, njc);
+    const bool pl = phys & 1, pr = phys & 2, pb = phys & 4, pt = phys & 8;
+    const int Iw = (pl && I == 1) ? 1 : I - 1, Ie = (pr && I == nic) ? nic : I + 1;
+    const long long col = (long long)(2 * I - 1) + kXOff;
+    auto row = [&](int j) { return (long long)(j + kYOff) * pitch + col; };
+    auto crow = [&](int J) { return e_off + (long long)(J + kYOff) * pitch_c + kXOff; };
+    const int nj = 2 * njc;
+
+    long long c = crow((pb && J0 == 1) ? 1 : J0 - 1);
+    double sw = e[c + Iw], sc = e[c + I], se = e[c + Ie];  // coarse row J-1
+    c = crow(J0);
+    double mw = e[c + Iw], mc = e[c + I], me = e[c + Ie];  // coarse row J
+    for (int J = J0; J <= J1; ++J) {
+        c = crow((pt && J == njc) ? njc : J + 1);
+        const double nw = e[c + Iw], nc = e[c + I], ne = e[c + Ie];  // coarse row J+1
+        const long long ra = row(2 * J - 1), rb = row(2 * J);
+        const double2 a = ld2(p + ra), b = ld2(p + rb);
+        const double a0 = a.x + mg_interp(mc, mw, sc, sw);
+        const double a1 = a.y + mg_interp(mc, me, sc, se);
+        const double b0 = b.x + mg_interp(mc, mw, nc, nw);
+        const double b1 = b.y + mg_interp(mc, me, nc, ne);
+        st2(p + ra, a0, a1);
+        st2(p + rb, b0, b1);
+        if (pl && I == 1) {
+            p[ra - 1] = a0;
+            p[rb - 1] = b0;
+        }
+        if (pr && I == nic) {
+            p[ra + 2] = a1;
+            p[rb + 2] = b1;
+        }
+        if (pb && J == 1) st2(p + row(0), a0, a1);
+        if (pt && J == njc) st2(p + row(nj + 1), b0, b1);
+        sw = mw, sc = mc, se = me;
+        mw = nw, mc = nc, me = ne;
+    }
+}
+
+// The hand-over of a decomposed hierarchy to its whole-domain levels
+// (misor_comm.hip allgather_blocks): the equal bw x bh blocks of the ranks of
+// a process grid with dims1 ranks along y, block q = (q / dims1, q % dims1)
+// covering cells (cx bw + 1 .., cy bh + 1 ..) of the padded whole-domain field,
+// and buf, which holds blocks packed row by row.  PACK copies block q0 of the
+// field to the start of buf; otherwise blocks q0 .. q0 + nq - 1 of buf (block
+// q at q bw bh) go to the field, except block skip.  V doubles per access:
+// with bw even every row segment starts on a 16-byte boundary in both.
+template <int V, bool PACK>
+__global__ void mg_block_copy_kernel(double* field, long long pitch, double* buf, int bw, int bh,
+                                     int dims1, int q0, int nq, int skip) {
+    const int rw = bw / V;  // accesses per block row
+    const long long per = (long long)rw * bh;
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= per * nq) return;
+    const int q = q0 + (int)(k / per);
+    if (!PACK && q == skip) return;
+    const long long r = k % per;
+    const int j = (int)(r / rw), i = (int)(r % rw) * V;
+    double* cell = field + (long long)((q % dims1) * bh + j + 1 + kYOff) * pitch +
+                   ((q / dims1) * bw + i + 1 + kXOff);
+    double* slot = buf + (PACK ? 0 : (long long)q * bw * bh) + (long long)j * bw + i;
+    if (V == 2) {
+        if (PACK)
+            *reinterpret_cast<double2*>(slot) = *reinterpret_cast<const double2*>(cell);
+        else
+            *reinterpret_cast<double2*>(cell) = *reinterpret_cast<const double2*>(slot);
+    } else {
+        if (PACK)
+            *slot = *cell;
+        else
+            *cell = *slot;
+    }
+}
+
+template <bool PACK>
+void launch_block_copy(hipStream_t s, double* field, long long pitch, double* buf, int bw, int bh,
+                       int dims1, int q0, int nq, int skip) {
+    const int V = (bw & 1) ? 1 : 2;
+    const long long n = (long long)(bw / V) * bh * nq;
+    if (n <= 0) return;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (V == 2)
+        hipLaunchKernelGGL((mg_block_copy_kernel<2, PACK>), grid, dim3(256), 0, s, field, pitch,
+                           buf, bw, bh, dims1, q0, nq, skip);
+    else
+        hipLaunchKernelGGL((mg_block_copy_kernel<1, PACK>), grid, dim3(256), 0, s, field, pitch,
+                           buf, bw, bh, dims1, q0, nq, skip);
+}
+
 }  // namespace
+
+void launch_mg_prolong_correct_dist(hipStream_t s, double* p, const double* e, long long e_off,
+                                    int phys, int nic, int njc, long long pitch,
+                                    long long pitch_c) {
+    const dim3 grid((nic + kMgTileW - 1) / kMgTileW, (njc + kMgTileH - 1) / kMgTileH);
+    hipLaunchKernelGGL(mg_prolong_correct_dist_kernel, grid, dim3(kMgTileW), 0, s, p, e, e_off,
+                       phys, nic, njc, pitch, pitch_c);
+}
+
+void launch_mg_block_pack(hipStream_t s, const double* field, long long pitch, double* buf, int bw,
+                          int bh, int dims1, int q) {
+    launch_block_copy<true>(s, const_cast<double*>(field), pitch, buf, bw, bh, dims1, q, 1, -1);
+}
+
+void launch_mg_block_scatter(hipStream_t s, double* field, long long pitch, const double* buf,
+                             int bw, int bh, int dims1, int nblocks, int skip) {
+    launch_block_copy<false>(s, field, pitch, const_cast<double*>(buf), bw, bh, dims1, 0, nblocks,
+                             skip);
+}
 
 void launch_mg_residual_restrict(hipStream_t s, const double* p, const double* rhs, double* rc,
                                  int nic, int njc, long long pitch, long long pitch_c,

@@ -113,11 +113,13 @@ void misor_destroy(misor_grid* g) {
     for (auto& v : g->nev)
         for (auto e : v) (void)hipEventDestroy(e);
     for (hipEvent_t e : {g->lx_pk, g->lx_cp, g->la_val[0], g->la_val[1], g->la_rd[0], g->la_rd[1],
-                         g->la_cmb[0], g->la_cmb[1]})
+                         g->la_cmb[0], g->la_cmb[1], g->ag_pk, g->ag_cp})
         if (e) (void)hipEventDestroy(e);
     (void)hipFree(g->la_stage);
     (void)hipFree(g->la_gather);
-    if (g->comm) ncclCommDestroy(g->comm);
+    (void)hipFree(g->ag_send);
+    (void)hipFree(g->ag_recv);
+    if (g->comm && !g->comm_owner) ncclCommDestroy(g->comm);
     if (g->own_stream && g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -182,10 +184,10 @@ static int alloc_state(misor_grid* g) {
 
 // a decomposed grid's transport: neighbour table, halo plans, communication
 // stream and events, halo buffers, and the in-process group or RCCL
-static int comm_setup(misor_grid* g, bool proxy) {
+static int comm_setup(misor_grid* g, bool proxy, misor_grid* parent, int level) {
     const misor_desc* d = &g->desc;
     const misor_local& L = g->loc;
-    if (!d->comm_id) return fail(MISOR_EINVAL, "nranks > 1 needs comm_id");
+    if (!d->comm_id && !parent) return fail(MISOR_EINVAL, "nranks > 1 needs comm_id");
     neighbours8(L.dims, L.coords, g->nbr);
     if (proxy) {  // (MISOR_PROXY_SIDES: every neighbour is rank 0; corners where both sides have one)
         const int* nb = L.neighbours;
@@ -218,17 +220,34 @@ static int comm_setup(misor_grid* g, bool proxy) {
     if (hipMalloc(&g->sendbuf, hb) != hipSuccess || hipMalloc(&g->recvbuf, hb) != hipSuccess)
         return fail(MISOR_ENOMEM, "halo buffer allocation failed");
     char name[MISOR_COMM_ID_BYTES + 1];
+    // a multigrid level of an in-process group: a group of its own, whose name
+    // every rank derives from the parent's group and the level
+    char derived[MISOR_COMM_ID_BYTES + 1] = {};
+    const void* id = d->comm_id;
+    if (parent && parent->local) {
+        if (snprintf(derived, sizeof derived, "%s/mg%d", parent->local_name, level) >=
+            MISOR_COMM_ID_BYTES)
+            return fail(MISOR_EINVAL, "local group %s: name too long for its multigrid levels",
+                        parent->local_name);
+        id = derived;
+    } else if (parent) {
+        g->comm = parent->comm;
+        g->comm_owner = parent->comm_owner ? parent->comm_owner : parent;
+        if (!g->comm) return fail(MISOR_ECOMM, "the communicator was aborted by an earlier error");
+        return MISOR_OK;
+    }
     // (no host scratch: this all-reduce stages on the device, la_stage / la_gather)
-    const LocalJoin joined =
-        join_local_group(d->comm_id, d->nranks, d->rank, g, 0, g->local, name);
+    const LocalJoin joined = join_local_group(id, d->nranks, d->rank, g, 0, g->local, name);
     if (joined == LocalJoin::kBadMember)
         return fail(MISOR_EINVAL, "local group %s: bad rank/size", name);
     if (joined == LocalJoin::kJoined) {
+        memcpy(g->local_name, name, sizeof name);
         bool lok = hipMalloc(&g->la_stage, sizeof(double) * 2 * kMaxT) == hipSuccess &&
                    hipMalloc(&g->la_gather, sizeof(double) * 2 * kMaxT * (size_t)d->nranks) ==
                        hipSuccess;
         for (hipEvent_t* e : {&g->lx_pk, &g->lx_cp, &g->la_val[0], &g->la_val[1],
-                              &g->la_rd[0], &g->la_rd[1], &g->la_cmb[0], &g->la_cmb[1]})
+                              &g->la_rd[0], &g->la_rd[1], &g->la_cmb[0], &g->la_cmb[1],
+                              &g->ag_pk, &g->ag_cp})
             lok = lok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
         g->local->barrier();  // every member registered before any exchange
         if (!lok) return fail(MISOR_EHIP, "in-process transport allocation failed");
@@ -241,7 +260,8 @@ static int comm_setup(misor_grid* g, bool proxy) {
     return MISOR_OK;
 }
 
-int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
+int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only, misor_grid* comm_parent,
+                int level) {
     if (!out || !d) return fail(MISOR_EINVAL, "null argument");
     *out = nullptr;
     if (d->imax < 2 || d->jmax < 2) return fail(MISOR_EINVAL, "imax, jmax must be >= 2");
@@ -281,7 +301,7 @@ int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
     g->loc = L;
     // a comm id with nranks == 1 still runs the decomposed code path (one rank, no
     // neighbours): lets the RCCL / overlap machinery be exercised on one GPU
-    g->dist = nranks > 1 || d->comm_id != nullptr;
+    g->dist = nranks > 1 || d->comm_id != nullptr || comm_parent != nullptr;
     g->np = g->dist ? 3 : 2;
     if (d->device >= 0) {
         g->device = d->device;
@@ -324,7 +344,7 @@ int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only) {
     }
     CREATE_STEP(set_geometry(g));
     CREATE_STEP(alloc_state(g));
-    if (g->dist) CREATE_STEP(comm_setup(g, proxy));
+    if (g->dist) CREATE_STEP(comm_setup(g, proxy, comm_parent, level));
     if (configure_tb(g, default_tsteps(tb_input(g), kDefaultTbVariant), kDefaultTbVariant, 0) !=
         MISOR_OK)
         CREATE_FAIL(MISOR_ENOMEM, "%s", g_err.c_str());

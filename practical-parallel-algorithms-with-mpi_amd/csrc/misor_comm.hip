@@ -73,6 +73,10 @@ int wait_stream(misor_grid* g, hipStream_t s) {
             (void)ncclCommAbort(g->comm);
             g->comm = nullptr;
             g->comm_dead = true;
+            if (g->comm_owner) {  // (a multigrid level on the communicator of the grid above)
+                g->comm_owner->comm = nullptr;
+                g->comm_owner->comm_dead = true;
+            }
             if (bad)
                 return fail(MISOR_ECOMM, "RCCL asynchronous error: %s", ncclGetErrorString(ar));
             return fail(MISOR_ECOMM, "communication made no progress for %.0f s "
@@ -192,6 +196,59 @@ int allreduce(misor_grid* g, double* dev, int n, int is_max, hipStream_t s) {
     }
     NCCLCHK(ncclAllReduce(dev, dev, n, ncclDouble, is_max ? ncclMax : ncclSum, g->comm, s));
     if (timed) HIPCHK(hipEventRecord(t1, s));
+    return MISOR_OK;
+}
+
+// The bw x bh blocks of all ranks into the whole-domain array `field`, of which
+// every rank has filled in its own (misor_grid.h): pack kernel, transport,
+// scatter kernel.  The blocks are equal, so RCCL's all-gather takes them as
+// they are; in-process every rank copies its peers' packed blocks, ordered by
+// events like exchange().
+int allgather_blocks(misor_grid* g, double* field, long long pitch, int bw, int bh) {
+    COMMCHK(g);
+    hipStream_t s = g->stream;
+    const int n = g->desc.nranks, rank = g->desc.rank, dims1 = g->loc.dims[1];
+    const long long blk = (long long)bw * bh;
+    if (g->ag_cap < blk * n) {
+        HIPCHK(hipStreamSynchronize(s));
+        if (g->local)  // (no peer still copies from the buffer given up: recorded before barrier 2)
+            for (misor_grid* o : g->local->members) HIPCHK(hipEventSynchronize(o->ag_cp));
+        (void)hipFree(g->ag_send);
+        (void)hipFree(g->ag_recv);
+        g->ag_send = g->ag_recv = nullptr;
+        g->ag_cap = 0;
+        if (hipMalloc(&g->ag_send, sizeof(double) * (size_t)blk) != hipSuccess ||
+            hipMalloc(&g->ag_recv, sizeof(double) * (size_t)(blk * n)) != hipSuccess)
+            return fail(MISOR_ENOMEM, "all-gather buffer allocation failed");
+        g->ag_cap = blk * n;
+    }
+    if (g->local) {
+        // as exchange(): my peers' copies of my packed block and my own scatter
+        // of the previous call are done before I pack again; my copies of q's
+        // block wait for q's pack.  Barrier 1: every rank has recorded its pack
+        // event (and allocated its buffer); barrier 2: its copy event.
+        LocalGroup<misor_grid>& G = *g->local;
+        for (int q = 0; q < n; ++q) HIPCHK(hipStreamWaitEvent(s, G.members[q]->ag_cp, 0));
+        launch_mg_block_pack(s, field, pitch, g->ag_send, bw, bh, dims1, rank);
+        HIPCHK(hipEventRecord(g->ag_pk, s));
+        G.barrier();
+        for (int q = 0; q < n; ++q) {
+            if (q == rank) continue;
+            const misor_grid* o = G.members[q];
+            HIPCHK(hipStreamWaitEvent(s, o->ag_pk, 0));
+            HIPCHK(hipMemcpyAsync(g->ag_recv + q * blk, o->ag_send, sizeof(double) * (size_t)blk,
+                                  hipMemcpyDeviceToDevice, s));
+        }
+        launch_mg_block_scatter(s, field, pitch, g->ag_recv, bw, bh, dims1, n, rank);
+        HIPCHK(hipEventRecord(g->ag_cp, s));
+        HIPCHK(hipGetLastError());
+        G.barrier();
+        return MISOR_OK;
+    }
+    launch_mg_block_pack(s, field, pitch, g->ag_send, bw, bh, dims1, rank);
+    NCCLCHK(ncclAllGather(g->ag_send, g->ag_recv, (size_t)blk, ncclDouble, g->comm, s));
+    launch_mg_block_scatter(s, field, pitch, g->ag_recv, bw, bh, dims1, n, rank);
+    HIPCHK(hipGetLastError());
     return MISOR_OK;
 }
 

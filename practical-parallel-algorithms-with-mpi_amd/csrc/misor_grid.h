@@ -136,10 +136,15 @@ struct misor_grid {
     // multi-GPU
     bool dist = false;
     ncclComm_t comm = nullptr;
+    // a distributed multigrid level (misor_mg.hip) runs on the communicator of
+    // the grid above it: it neither owns nor destroys it, and an abort reaches
+    // the owner too (wait_stream)
+    misor_grid* comm_owner = nullptr;
     int nbr[kDirs] = {-1, -1, -1, -1, -1, -1, -1, -1};  // L R B T BL BR TL TR
     HaloPlan plan[kMaxHaloDepth + 1] = {};               // by halo depth 1 .. max_depth
     int max_depth = 2;                                   // deepest plan built
     std::shared_ptr<LocalGroup<misor_grid>> local;       // in-process transport (local_group.h)
+    char local_name[MISOR_COMM_ID_BYTES + 1] = {};       // its group's name ("LOCAL:...")
     bool overlap = true;            // exchange on cstream while the interior sweeps
     hipStream_t cstream = nullptr;  // communication stream
     hipEvent_t ev_s = nullptr, ev_x = nullptr;
@@ -160,6 +165,13 @@ struct misor_grid {
     double* la_stage = nullptr;   // 2 x kMaxT: my value, by all-reduce parity
     double* la_gather = nullptr;  // 2 x nranks x kMaxT: every rank's value, by parity
     long long la_gen = 0;
+    // allgather_blocks (the hand-over of misor_solve_mg_dist): my block packed,
+    // every rank's block in rank order; in-process: my block packed / my copies
+    // and scatter done
+    double* ag_send = nullptr;
+    double* ag_recv = nullptr;
+    long long ag_cap = 0;  // doubles in ag_recv
+    hipEvent_t ag_pk = nullptr, ag_cp = nullptr;
     bool comm_dead = false;       // the RCCL communicator was aborted (error / timeout)
     // communication timing inside a timed solve: start/stop event pairs of the
     // halo exchanges (0) and residual all-reduces (1) of the current batch
@@ -216,12 +228,21 @@ inline double near_band_abs(double near_rel, double epssq) {
 }
 // misor_create; poisson_only: a grid that only ever solves (a multigrid level)
 // -- the NS fields u, v, f, g are not allocated
-MISOR_HIDDEN int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only);
+// comm_parent: the new grid is level `level` of comm_parent's distributed
+// multigrid hierarchy, decomposed like it (d->nranks, rank, dims) and on its
+// communicator instead of d->comm_id: the same ncclComm_t, not owned, or an
+// in-process group of its own named from the parent's group and the level
+MISOR_HIDDEN int grid_create(misor_grid** out, const misor_desc* d, bool poisson_only,
+                             misor_grid* comm_parent = nullptr, int level = 0);
 MISOR_HIDDEN int grid_adopt(misor_grid* g, const double* p_dev, const double* rhs_dev,
                             double omega, double eps, int itermax);
 
 // misor_comm.hip
 MISOR_HIDDEN int allreduce(misor_grid* g, double* dev, int n, int is_max, hipStream_t s = nullptr);
+// every rank's bw x bh block (equal blocks: rank q at (q / dims[1], q % dims[1]))
+// of the padded whole-domain array `field` of row pitch `pitch`, which holds
+// this rank's own block, into the same array on every rank; on g's stream
+MISOR_HIDDEN int allgather_blocks(misor_grid* g, double* field, long long pitch, int bw, int bh);
 MISOR_HIDDEN int collect_comm_times(misor_grid* g);
 MISOR_HIDDEN int exchange(misor_grid* g, double* field, int d, hipStream_t s = nullptr);
 MISOR_HIDDEN int gather(misor_grid* g, const double* field, double* host);

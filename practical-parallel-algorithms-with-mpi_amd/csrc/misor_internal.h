@@ -177,6 +177,20 @@ void launch_mg_residual_restrict(hipStream_t s, const double* p, const double* r
 // p += bilinear interpolation of e, then p's ghost copy
 void launch_mg_prolong_correct(hipStream_t s, double* p, const double* e, int nic, int njc,
                                long long pitch, long long pitch_c);
+// the same on a rank's block of a decomposed level: e + e_off is cell (0, 0) of
+// the coarse array as the block sees it, phys the mask of the block's physical
+// sides (bit 0 left, 1 right, 2 bottom, 3 top); a side that borders another
+// rank reads the coarse halo cell and writes no ghost
+void launch_mg_prolong_correct_dist(hipStream_t s, double* p, const double* e, long long e_off,
+                                    int phys, int nic, int njc, long long pitch,
+                                    long long pitch_c);
+// equal bw x bh blocks of a process grid (dims1 ranks along y) and a padded
+// whole-domain field: block q of the field packed into buf; blocks 0 ..
+// nblocks - 1 of buf (block q at q bw bh) into the field, except block skip
+void launch_mg_block_pack(hipStream_t s, const double* field, long long pitch, double* buf, int bw,
+                          int bh, int dims1, int q);
+void launch_mg_block_scatter(hipStream_t s, double* field, long long pitch, const double* buf,
+                             int bw, int bh, int dims1, int nblocks, int skip);
 
 // The tail of a hierarchy -- its trailing levels that each fit the LDS of one
 // workgroup (small_solve_fits) -- cycled in ONE launch of one workgroup

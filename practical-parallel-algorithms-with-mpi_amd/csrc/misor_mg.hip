@@ -18,9 +18,18 @@
 // the cycles runs in the kernel too.  The bits are those of the level-by-level
 // path.
 //
+// A decomposed grid is cycled by misor_solve_mg_dist (DESIGN.md "Geometric
+// multigrid, decomposed"; the level split is mg_dist_plan.h's): its first
+// levels are decomposed grids themselves, on the same process grid and the
+// communicator of level 0, smoothed and solved by the same solve_with; below
+// them every rank holds the whole domain -- an internal single-rank grid with
+// a hierarchy of its own, cycled by cycle() redundantly on every rank after
+// the restricted blocks have been all-gathered into its rhs.
+//
 // Every argument check precedes the first HIP call.
 
 #include "misor_grid.h"
+#include "mg_dist_plan.h"
 
 struct MgHierarchy {
     int coarse_cells = -1;
@@ -42,20 +51,17 @@ struct MgHierarchy {
     std::vector<MgTailLevel> tail_lv_up;
     MgTailState tail_up{};
     bool tail_st_valid = false;
+    // the decomposed form (misor_solve_mg_dist): the distributed levels,
+    // dlv[0] the user's grid (not owned), and the first gathered level (null:
+    // every level is distributed), whose own hierarchy holds the rest
+    int dist_coarse_cells = -1, dist_gather_cells = -1;
+    std::vector<misor_grid*> dlv;
+    misor_grid* gath = nullptr;
 };
 
 namespace {
 
 constexpr size_t kMgEventPairs = 64;  // pairs held before they are resolved
-
-// next level's shape, or false where (ni, nj) is the coarsest
-bool mg_coarsen(int ni, int nj, int coarse_cells, int* nic, int* njc) {
-    if ((ni & 1) || (nj & 1) || ni < 4 || nj < 4) return false;
-    if ((long long)ni * nj <= (long long)coarse_cells) return false;
-    *nic = ni / 2;
-    *njc = nj / 2;
-    return true;
-}
 
 int check_params(const misor_mg_params& q) {
     if (q.nu1 < 0 || q.nu2 < 0)
@@ -125,6 +131,13 @@ void free_levels(MgHierarchy* h) {
     h->tail_lv_up.clear();
     h->tail_st_valid = false;
     h->tail_first = h->tail_count = 0;
+}
+
+void free_dist_levels(MgHierarchy* h) {
+    for (size_t l = 1; l < h->dlv.size(); ++l) misor_destroy(h->dlv[l]);
+    h->dlv.clear();
+    misor_destroy(h->gath);
+    h->gath = nullptr;
 }
 
 // first index and length of the maximal run of trailing levels that fit the
@@ -390,11 +403,192 @@ int cycle(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
     return cycle_up(g0, q, l, res);
 }
 
+// ---- the decomposed form (misor_solve_mg_dist) ----
+
+// a level of the hierarchy of g: nic x njc cells of (dx, dy), one rank's whole
+// grid (parent null) or decomposed like g on its communicator
+int create_level(misor_grid* g, int nic, int njc, double dx, double dy, misor_grid* parent,
+                 int level, misor_grid** out) {
+    misor_desc d{};
+    d.imax = nic;
+    d.jmax = njc;
+    d.dx = dx;
+    d.dy = dy;
+    d.omega = 1.0;
+    d.variant = MISOR_SOLVE_RB;
+    d.device = g->device;
+    d.nranks = 1;
+    if (parent) {
+        d.nranks = g->desc.nranks;
+        d.rank = g->desc.rank;
+        d.dims[0] = g->loc.dims[0];
+        d.dims[1] = g->loc.dims[1];
+    }
+    return grid_create(out, &d, true, parent, level);
+}
+
+// (re)build the levels below the decomposed grid g for plan P: collective, and
+// every rank rebuilds at the same calls (the plan's arguments are the same on
+// every rank).  Streams as in ensure_hierarchy.
+int ensure_dist_hierarchy(misor_grid* g, int coarse_cells, int gather_cells, const MgDistPlan& P) {
+    if (!g->mg) g->mg = new MgHierarchy();
+    MgHierarchy* h = g->mg;
+    if (h->dist_coarse_cells != coarse_cells || h->dist_gather_cells != gather_cells ||
+        h->dlv.empty()) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        free_dist_levels(h);
+        h->dist_coarse_cells = coarse_cells;
+        h->dist_gather_cells = gather_cells;
+        h->dlv.push_back(g);
+        int ni = g->desc.imax, nj = g->desc.jmax;
+        double dx = g->desc.dx, dy = g->desc.dy;
+        int rc = MISOR_OK;
+        for (int l = 1; l <= P.ndist && l < P.nlevels && !rc; ++l) {
+            ni /= 2;
+            nj /= 2;
+            dx *= 2.0;
+            dy *= 2.0;
+            misor_grid* c = nullptr;
+            const bool dist = l < P.ndist;
+            rc = create_level(g, ni, nj, dx, dy, dist ? g : nullptr, l, &c);
+            if (rc) break;
+            if (!dist) {
+                h->gath = c;
+                break;
+            }
+            const misor_grid* f = h->dlv.back();
+            h->dlv.push_back(c);
+            // the halved block is the block of the halved grid (mg_dist_plan.h)
+            if (2 * c->loc.ni != f->loc.ni || 2 * c->loc.nj != f->loc.nj ||
+                2 * c->loc.ioff != f->loc.ioff || 2 * c->loc.joff != f->loc.joff)
+                rc = fail(MISOR_ESTATE, "misor_solve_mg_dist: level %d is not the halved block", l);
+        }
+        if (rc) {
+            free_dist_levels(h);
+            return rc;
+        }
+    }
+    for (size_t l = 1; l < h->dlv.size(); ++l) {
+        misor_grid* c = h->dlv[l];
+        if (c->stream != g->stream) MISOR_TRY(misor_set_stream(c, g->stream));
+        c->near_rel = g->near_rel;
+        c->near_exp = g->near_exp;
+    }
+    if (misor_grid* G = h->gath) {
+        if (G->stream != g->stream) MISOR_TRY(misor_set_stream(G, g->stream));
+        G->near_rel = g->near_rel;
+        G->near_exp = g->near_exp;
+        G->mg_tail = g->mg_tail;
+        MISOR_TRY(ensure_hierarchy(G, coarse_cells));
+    }
+    return MISOR_OK;
+}
+
+int phys_mask(const misor_grid* f) {
+    int m = 0;
+    for (int k = 0; k < 4; ++k)
+        if (f->loc.neighbours[k] < 0) m |= 1 << k;
+    return m;
+}
+
+// One cycle on distributed level l of the decomposed grid g0; *res as cycle()'s.
+int cycle_dist(misor_grid* g0, const misor_mg_params& q, size_t l, double* res) {
+    MgHierarchy* h = g0->mg;
+    misor_grid* f = h->dlv[l];
+    const bool last = l + 1 == h->dlv.size();
+    if (last && !h->gath) {  // the coarsest level, decomposed
+        int it = 0;
+        return solve_with(f, q.omega_coarse, q.eps_coarse, q.itermax_coarse, &it, res);
+    }
+    const bool timed = l == 0 && g0->timing;
+    const int nic = f->loc.ni / 2, njc = f->loc.nj / 2;
+    MISOR_TRY(smooth(f, q.omega_smooth, q.nu1, res));
+    // the residual of a cell at a block edge reads the neighbour's p
+    MISOR_TRY(p_halo(f));
+    double unused = 0.0;
+    if (!last) {
+        misor_grid* c = h->dlv[l + 1];
+        if (timed) MISOR_TRY(record_transfer(g0, 0));
+        launch_mg_residual_restrict(g0->stream, pbuf(f, f->cur), f->fld[kRhs], c->fld[kRhs], nic,
+                                    njc, f->pitch, c->pitch, f->sp.idx2, f->sp.idy2);
+        HIPCHK(hipGetLastError());
+        if (timed) MISOR_TRY(record_transfer(g0, -1));
+        c->rhs_halo = 0;  // rc is new: its halo is exchanged by the level's next solve
+        // e = 0 over the whole local array, the inter-rank halo included
+        HIPCHK(hipMemsetAsync(pbuf(c, c->cur), 0, (size_t)c->elems * sizeof(double), g0->stream));
+        c->p_stale = false;
+        MISOR_TRY(cycle_dist(g0, q, l + 1, &unused));
+        // the interpolation at a block edge reads the neighbours' e, corners too
+        double* e = pbuf(c, c->cur);
+        MISOR_TRY(exchange(c, e, 1));
+        if (timed) MISOR_TRY(record_transfer(g0, 1));
+        launch_mg_prolong_correct_dist(g0->stream, pbuf(f, f->cur), e, 0, phys_mask(f), nic, njc,
+                                       f->pitch, c->pitch);
+    } else {
+        // the hand-over: my restricted block into my window of the whole-domain
+        // rhs, everybody else's by the all-gather; then every rank cycles the
+        // gathered levels alone, the same bits everywhere
+        misor_grid* G = h->gath;
+        const long long win = (long long)(f->loc.joff / 2) * G->pitch + f->loc.ioff / 2;
+        if (timed) MISOR_TRY(record_transfer(g0, 0));
+        launch_mg_residual_restrict(g0->stream, pbuf(f, f->cur), f->fld[kRhs],
+                                    G->fld[kRhs] + win, nic, njc, f->pitch, G->pitch, f->sp.idx2,
+                                    f->sp.idy2);
+        HIPCHK(hipGetLastError());
+        if (timed) MISOR_TRY(record_transfer(g0, -1));
+        MISOR_TRY(allgather_blocks(f, G->fld[kRhs], G->pitch, nic, njc));
+        HIPCHK(hipMemset2DAsync(pbuf(G, G->cur) + (long long)kYOff * G->pitch + kXOff,
+                                (size_t)G->pitch * sizeof(double), 0,
+                                (size_t)(G->loc.ni + 2) * sizeof(double), (size_t)G->loc.nj + 2,
+                                g0->stream));
+        MISOR_TRY(cycle(G, q, 0, &unused));
+        if (timed) MISOR_TRY(record_transfer(g0, 1));
+        launch_mg_prolong_correct_dist(g0->stream, pbuf(f, f->cur), pbuf(G, G->cur), win,
+                                       phys_mask(f), nic, njc, f->pitch, G->pitch);
+    }
+    HIPCHK(hipGetLastError());
+    if (timed) MISOR_TRY(record_transfer(g0, -1));
+    f->p_stale = true;  // p changed up to the block edge: its halo is the neighbours' old p
+    return smooth(f, q.omega_smooth, q.nu2, res);
+}
+
+// misor_solve_mg past its checks, on a grid that is not decomposed
+int solve_mg_single(misor_grid* g, const misor_mg_params& q, int* cycles, double* res) {
+    HIPCHK(hipSetDevice(g->device));
+    MISOR_TRY(ensure_hierarchy(g, q.coarse_cells));
+    const double epssq = g->desc.eps * g->desc.eps;
+    int n = 0;
+    double r = 1.0;  // as solveRB's loop (solver.c:196)
+    int rc = MISOR_OK;
+    g->stats.mg_tail_levels = 0;
+    g->stats.mg_dist_levels = 0;
+    if (tail_fused(g) && g->mg->tail_first == 0) {
+        // the grid itself fits: the loop runs in the kernel, which comes back
+        // before the end only where the host had a cycle to finish
+        while (!rc && (r >= epssq) && (n < q.maxcycles))
+            rc = tail_run(g, q, epssq, q.maxcycles, &n, &r);
+    } else {
+        while ((r >= epssq) && (n < q.maxcycles)) {
+            rc = cycle(g, q, 0, &r);
+            if (rc) break;
+            ++n;
+        }
+    }
+    g->stats.mg_cycles = n;
+    g->stats.mg_levels = (int)g->mg->lv.size();
+    if (rc) return rc;
+    MISOR_TRY(collect_transfer_times(g));
+    if (cycles) *cycles = n;
+    if (res) *res = r;
+    return MISOR_OK;
+}
+
 }  // namespace
 
 void mg_free(misor_grid* g) {
     if (!g->mg) return;
     free_levels(g->mg);
+    free_dist_levels(g->mg);
     for (hipEvent_t e : g->mg->ev) (void)hipEventDestroy(e);
     delete g->mg;
     g->mg = nullptr;
@@ -404,6 +598,9 @@ int mg_set_stream(misor_grid* g, hipStream_t s) {
     if (!g->mg) return MISOR_OK;
     for (size_t l = 1; l < g->mg->lv.size(); ++l)
         MISOR_TRY(misor_set_stream(g->mg->lv[l], s));
+    for (size_t l = 1; l < g->mg->dlv.size(); ++l)
+        MISOR_TRY(misor_set_stream(g->mg->dlv[l], s));
+    if (g->mg->gath) MISOR_TRY(misor_set_stream(g->mg->gath, s));
     return MISOR_OK;
 }
 
@@ -453,29 +650,57 @@ int misor_solve_mg(misor_grid* g, const misor_mg_params* prm, int* cycles, doubl
     if (g->desc.variant != MISOR_SOLVE_RB)
         return fail(MISOR_EINVAL, "misor_solve_mg smooths with solveRB (variant RB)");
     if (g->dist)
-        return fail(MISOR_ESTATE, "misor_solve_mg has no decomposed form yet (single rank only)");
+        return fail(MISOR_ESTATE,
+                    "misor_solve_mg is the single-rank form: a decomposed grid is cycled by "
+                    "misor_solve_mg_dist");
+    return solve_mg_single(g, prm ? *prm : default_params(g), cycles, res);
+}
+
+int misor_mg_dist_levels(int nranks, const int dims_in[2], int imax, int jmax, int coarse_cells,
+                         int gather_cells, int* nlevels, int* ndist) {
+    if (!nlevels || !ndist) return fail(MISOR_EINVAL, "misor_mg_dist_levels: null nlevels or ndist");
+    MgDistPlan P{};
+    char err[kDecompErr];
+    const int rc = mg_dist_plan(nranks, dims_in, imax, jmax, coarse_cells, gather_cells, &P, err);
+    if (rc) return fail(rc, "%s", err);
+    *nlevels = P.nlevels;
+    *ndist = P.ndist;
+    return MISOR_OK;
+}
+
+int misor_solve_mg_dist(misor_grid* g, const misor_mg_params* prm, int gather_cells, int* cycles,
+                        double* res) {
+    if (prm) MISOR_TRY(check_params(*prm));
+    if (!g) return fail(MISOR_EINVAL, "misor_solve_mg_dist: null grid");
+    if (g->desc.variant != MISOR_SOLVE_RB)
+        return fail(MISOR_EINVAL, "misor_solve_mg_dist smooths with solveRB (variant RB)");
     const misor_mg_params q = prm ? *prm : default_params(g);
+    if (!g->dist) return solve_mg_single(g, q, cycles, res);
+    if (gather_cells < 0) gather_cells = kMgGatherCells;
+    MgDistPlan P{};
+    char err[kDecompErr];
+    const int prc = mg_dist_plan(g->desc.nranks, g->loc.dims, g->desc.imax, g->desc.jmax,
+                                 q.coarse_cells, gather_cells, &P, err);
+    if (prc) return fail(prc, "%s", err);
     HIPCHK(hipSetDevice(g->device));
-    MISOR_TRY(ensure_hierarchy(g, q.coarse_cells));
+    MISOR_TRY(ensure_dist_hierarchy(g, q.coarse_cells, gather_cells, P));
+    if (g->mg->gath) g->mg->gath->stats.mg_tail_levels = 0;
     const double epssq = g->desc.eps * g->desc.eps;
     int n = 0;
     double r = 1.0;  // as solveRB's loop (solver.c:196)
     int rc = MISOR_OK;
-    g->stats.mg_tail_levels = 0;
-    if (tail_fused(g) && g->mg->tail_first == 0) {
-        // the grid itself fits: the loop runs in the kernel, which comes back
-        // before the end only where the host had a cycle to finish
-        while (!rc && (r >= epssq) && (n < q.maxcycles))
-            rc = tail_run(g, q, epssq, q.maxcycles, &n, &r);
-    } else {
-        while ((r >= epssq) && (n < q.maxcycles)) {
-            rc = cycle(g, q, 0, &r);
-            if (rc) break;
-            ++n;
-        }
+    // res is level 0's all-reduced residual, the same bits on every rank: all
+    // ranks leave the loop after the same cycle
+    while ((r >= epssq) && (n < q.maxcycles)) {
+        rc = cycle_dist(g, q, 0, &r);
+        if (rc) break;
+        ++n;
     }
+    const misor_grid* G = g->mg->gath;
     g->stats.mg_cycles = n;
-    g->stats.mg_levels = (int)g->mg->lv.size();
+    g->stats.mg_levels = P.nlevels;
+    g->stats.mg_dist_levels = P.ndist;
+    g->stats.mg_tail_levels = G && n > 0 ? G->stats.mg_tail_levels : 0;
     if (rc) return rc;
     MISOR_TRY(collect_transfer_times(g));
     if (cycles) *cycles = n;

@@ -4,7 +4,9 @@
  *   exe-poisson-mg <file.par>  ->  prints the parameters and the cycle count
  *   (where exe-poisson prints the iteration count), writes p.dat in the same
  *   format and prints "Walltime %.2fs".  The .par's eps is the tolerance;
- *   omg and itermax are not used (misor_solve_mg's defaults).  Single rank.
+ *   omg and itermax are not used (misor_solve_mg's defaults).  Under
+ *   MISOR_RANKS=N (host/ranks.h) the domain is decomposed and the cycles are
+ *   misor_solve_mg_dist's, with its defaults; rank 0 prints.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,8 +26,8 @@ static int rank_main(const RankCtx* rk, void* arg)
 
     initSolver(&solver, &params, 2);
     startTime = getTimeStamp();
-    misorCheck(misor_solve_mg(solver.dev, NULL, &cycles, &res), "misor_solve_mg");
-    printf("%d ", cycles);
+    misorCheck(misor_solve_mg_dist(solver.dev, NULL, -1, &cycles, &res), "misor_solve_mg_dist");
+    if (rk->rank == 0) printf("%d ", cycles);
     endTime = getTimeStamp();
     writeResult(&solver, "p.dat");
 

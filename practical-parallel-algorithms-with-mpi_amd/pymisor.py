@@ -83,6 +83,11 @@ class StatsTail(Stats):
                 ("mg_tail_fallbacks", C.c_longlong), ("mg_tail_ms", C.c_double)]
 
 
+class StatsDist(StatsTail):
+    """misor_stats whole: StatsTail and what was appended after it"""
+    _fields_ = [("mg_dist_levels", C.c_int)]
+
+
 class MgInfo3(C.Structure):
     _fields_ = [("cycles", C.c_int), ("levels", C.c_int), ("transfer_ms", C.c_double * 2),
                 ("transfers", C.c_longlong)]
@@ -142,6 +147,10 @@ SIGNATURES = {
     "misor_mg_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), C.c_int]),
     "misor_solve_mg": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.POINTER(C.c_int), _dp]),
+    "misor_solve_mg_dist": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.c_int,
+                                      C.POINTER(C.c_int), _dp]),
+    "misor_mg_dist_levels": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "misor_ns_setup": (C.c_int, [C.c_void_p, C.POINTER(NsDesc)]),
     "misor_compute_timestep": (C.c_int, [C.c_void_p, C.c_double, C.c_double, _dp]),
     "misor_set_dt": (C.c_int, [C.c_void_p, C.c_double]),
@@ -155,7 +164,7 @@ SIGNATURES = {
     "misor_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "misor_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "misor_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
-    "misor_get_stats": (C.c_int, [C.c_void_p, C.POINTER(StatsTail)]),
+    "misor_get_stats": (C.c_int, [C.c_void_p, C.POINTER(StatsDist)]),
     "misor_reset_stats": (C.c_int, [C.c_void_p]),
     "misor_chain_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_longlong,
                                     C.POINTER(C.c_longlong)]),
@@ -268,6 +277,17 @@ def mg_tail(imax, jmax, coarse_cells=64):
     first, count = C.c_int(0), C.c_int(0)
     _check(lib().misor_mg_tail(imax, jmax, coarse_cells, C.byref(first), C.byref(count)))
     return first.value, count.value
+
+
+def mg_dist_levels(nranks, imax, jmax, coarse_cells=64, gather_cells=-1, dims=(0, 0)):
+    """(nlevels, ndist): the levels of an imax x jmax grid and how many of them
+    misor_solve_mg_dist keeps distributed over nranks (misor_mg_dist_levels;
+    host-only)"""
+    n, nd = C.c_int(0), C.c_int(0)
+    d = (C.c_int * 2)(*dims)
+    _check(lib().misor_mg_dist_levels(nranks, d, imax, jmax, coarse_cells, gather_cells,
+                                      C.byref(n), C.byref(nd)))
+    return n.value, nd.value
 
 
 def mg3_levels(imax, jmax, kmax, coarse_cells=512):
@@ -390,6 +410,21 @@ class Grid:
         _check(lib().misor_solve_mg(self.h, C.byref(q), C.byref(n), C.byref(res)))
         return n.value, res.value
 
+    def solve_mg_dist(self, gather_cells=-1, **params):
+        """multigrid V-cycles on a decomposed grid (misor_solve_mg_dist; collective):
+        (cycles, res).  gather_cells: blocks of at most this many cells are
+        gathered (-1: the default); the other keywords as solve_mg's"""
+        q = self.mg_default_params()
+        names = [f[0] for f in MgParams._fields_]
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError("solve_mg_dist: unknown parameter %r (one of %s)" % (k, names))
+            setattr(q, k, v)
+        n, res = C.c_int(0), C.c_double(0.0)
+        _check(lib().misor_solve_mg_dist(self.h, C.byref(q), gather_cells, C.byref(n),
+                                         C.byref(res)))
+        return n.value, res.value
+
     def synchronize(self):
         _check(lib().misor_synchronize(self.h))
 
@@ -445,7 +480,7 @@ class Grid:
         _check(lib().misor_enable_timing(self.h, 1 if on else 0))
 
     def stats(self):
-        s = StatsTail()
+        s = StatsDist()
         _check(lib().misor_get_stats(self.h, C.byref(s)))
         return {"sweeps": s.sweeps, "launches": s.launches, "sweep_ms": s.sweep_ms,
                 "timed_sweeps": s.timed_sweeps, "timed_passes": s.timed_passes,
@@ -457,7 +492,8 @@ class Grid:
                 "mg_levels": s.mg_levels, "mg_transfer_ms": list(s.mg_transfer_ms),
                 "mg_transfers": s.mg_transfers, "mg_tail_levels": s.mg_tail_levels,
                 "mg_tail_launches": s.mg_tail_launches,
-                "mg_tail_fallbacks": s.mg_tail_fallbacks, "mg_tail_ms": s.mg_tail_ms}
+                "mg_tail_fallbacks": s.mg_tail_fallbacks, "mg_tail_ms": s.mg_tail_ms,
+                "mg_dist_levels": s.mg_dist_levels}
 
     def reset_stats(self):
         _check(lib().misor_reset_stats(self.h))
