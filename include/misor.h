@@ -362,7 +362,10 @@ int misor_max_uv(misor_grid* g, double* umax, double* vmax);
 /* launch-geometry knobs of the sweep kernel (defaults chosen by measurement,
  * DESIGN.md); results are bit-identical for every setting */
 enum {
-    MISOR_TUNE_SWEEP_VARIANT = 1,  /* 0..7: strips per workgroup x rows in flight x nt stores */
+    MISOR_TUNE_SWEEP_VARIANT = 1,  /* 0..14 (default 7), an index into kSweepVariants
+                                    * (csrc/misor_internal.h): 4, 8 or 16 strips per
+                                    * workgroup x 1..3 rows in flight x non-temporal
+                                    * stores / loads; anything else is MISOR_EINVAL */
     MISOR_TUNE_ROWS_PER_BLOCK = 2, /* rows one workgroup marches; <= 0: automatic */
     MISOR_TUNE_XCD_REMAP = 3,      /* 1: adjacent blocks on one XCD (shared L2 halos) */
     MISOR_TUNE_SMALL_SOLVE = 4,    /* 1 (default): whole solve in one workgroup, p in LDS,
