@@ -624,7 +624,8 @@ int misor3_get_solve_time(const misor_grid3* g, double* ms, long long* iters);
 /* --- 3D multigrid: the V-cycle of misor_solve_mg above for lap p = rhs on one
  * misor_grid3 (DESIGN.md "Geometric multigrid, 3D" has the full definition).
  * Neumann by misor3_solve's ghost copy (faces only); smoother and coarsest
- * solver are misor3_solve's red-black iteration.  Single rank only.
+ * solver are misor3_solve's red-black iteration.  misor3_solve_mg is the
+ * single-rank form, misor3_solve_mg_dist below the one for slabs.
  *
  * Levels: level l+1 has (imax/2, jmax/2, kmax/2) cells of (2dx, 2dy, 2dz);
  * the coarsest is the first with an odd side, a side below 4, or
@@ -673,8 +674,61 @@ typedef struct {
     int cycles, levels;
     double transfer_ms[2];
     long long transfers;
+    /* the levels the last multigrid solve kept distributed over the ranks
+     * (misor3_mg_dist_levels' ndist); 0 after misor3_solve_mg and on a grid that
+     * is not decomposed */
+    int dist_levels;
 } misor3_mg_info;
 int misor3_get_mg_info(const misor_grid3* g, misor3_mg_info* out);
+
+/* The same cycle on a grid decomposed into slabs (misor3_create with nranks >
+ * 1): collective over the ranks of g; with one rank it is misor3_solve_mg, the
+ * same bits and the same misor3_mg_info.  Levels, smoothing, residual,
+ * restriction, trilinear weights, ghost copy, res and the loop over the cycles
+ * are those defined above, and p is bit for bit the single-rank
+ * misor3_solve_mg's for every slab count.  p's 2-deep halo is left current, as
+ * misor3_solve leaves it, and a later misor3_solve of the grid is what it would
+ * have been without this call.
+ *
+ * The first levels of the hierarchy stay distributed: level 0 always; level
+ * l >= 1 iff level l-1 is, every slab of level l-1 has an even number of
+ * planes, the halved slabs have at least 4 planes and more than gather_cells
+ * cells (imax_l * jmax_l * kloc_l; gather_cells < 0: the default, 2097152, the
+ * fastest value measured, DESIGN.md "Geometric multigrid, 3D, decomposed"),
+ * and level l is the coarsest level or its slabs have even plane counts again.
+ * "Every slab even" means nranks divides the level's kmax with an even
+ * quotient, so the slabs of a distributed level are equal and are
+ * misor3_decompose of the halved grid.  A distributed level is smoothed -- or,
+ * as the coarsest level, solved -- by the slab misor3_solve.  The remaining
+ * levels are gathered: every rank holds them whole.  At the hand-over the
+ * ranks' restricted slabs are all-gathered into the whole-domain rhs and every
+ * rank runs the single-rank cycle on the gathered levels redundantly (the same
+ * bits everywhere, nothing is sent back; these levels run the streaming sweep,
+ * not the resident launch); the correction reads the rank's window of the
+ * whole-domain e.
+ *
+ * res is level 0's all-reduced residual carry as misor3_solve reports it on
+ * slabs, the same bits on every rank, so all ranks run the same number of
+ * cycles.  It can differ from the single-rank res in its last bits (the sum's
+ * order differs): the cycle count is the single-rank one except where res
+ * lands within those bits of eps^2.
+ *
+ * Found before any device or collective call, by every rank from the same
+ * arithmetic, in this order: misor3_solve_mg's MISOR_EINVAL cases in its order;
+ * MISOR_ESTATE for a Cartesian grid (misor3_create_cart); MISOR_ESTATE for a
+ * hierarchy of two or more levels on level-0 slabs with an odd plane count (a
+ * one-level hierarchy on odd slabs is fine: its cycle is the decomposed
+ * coarsest solve).  The hierarchy is built by the first call, rebuilt when
+ * coarse_cells or the split changes and freed by misor3_destroy. */
+int misor3_solve_mg_dist(misor_grid3* g, const misor_mg_params* prm, int gather_cells,
+                         int* cycles, double* res);
+/* host-only: how misor3_solve_mg_dist splits the hierarchy of an imax x jmax x
+ * kmax grid over nranks slabs: *nlevels = misor3_mg_levels' count, the first
+ * *ndist of them distributed.  MISOR_EINVAL: misor3_decompose's and
+ * misor3_mg_levels' cases, a null nlevels or ndist; MISOR_ESTATE: the refusal
+ * above.  The outputs are untouched on an error. */
+int misor3_mg_dist_levels(int nranks, int imax, int jmax, int kmax, int coarse_cells,
+                          int gather_cells, int* nlevels, int* ndist);
 
 /* --- the box over a 3D Cartesian process grid (assignment-6/src/comm.c:24-101,
  * 476-513), a second decomposition beside the slabs.  A rank owns a block of

@@ -165,9 +165,17 @@ __global__ __launch_bounds__(kThreads) void mg3_residual_restrict_kernel(
 // of e in registers and shifts it up the march; a coarse plane of the tile
 // with its (clamped) rim passes through LDS once, loaded by the whole
 // workgroup.
-__global__ __launch_bounds__(kThreads) void mg3_prolong_correct_kernel(
+//
+// A slab of a decomposed grid (misor3_mg_dist.hip): lo_phys / hi_phys say
+// which z sides of the nkc coarse planes are physical.  On a physical side K is
+// clamped to the interior and the face ghost plane is written, as on a single
+// domain; on a side that faces a rank the coarse halo plane 0 / nkc + 1 is read
+// (x and y still clamped: no ghost column or row of it is read) and no ghost
+// plane is written.  With both flags set every expression is the single
+// domain's.
+__device__ __forceinline__ void mg3_prolong_correct_body(
     double* __restrict__ p, const double* __restrict__ e, int nic, int njc, int nkc, long long sx,
-    long long sxy, long long sxc, long long sxyc) {
+    long long sxy, long long sxc, long long sxyc, bool lo_phys, bool hi_phys) {
     __shared__ double tile[kCoarseH][kCoarseW];
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int tid = ty * kMg3TileW + tx;
@@ -179,10 +187,11 @@ __global__ __launch_bounds__(kThreads) void mg3_prolong_correct_kernel(
     const long long col = 2LL * I - 1;
     const long long ra = (2LL * J - 1) * sx + col, rb = ra + sx;
 
-    // coarse plane K (clamped) of the tile with its clamped rim into w[3][3]
-    // (w[y][x]: rows J-1 .. J+1, columns I-1 .. I+1)
+    // coarse plane K (clamped on a physical side) of the tile with its clamped
+    // rim into w[3][3] (w[y][x]: rows J-1 .. J+1, columns I-1 .. I+1)
     auto fetch = [&](int K, double (&w)[3][3]) {
-        const double* ek = e + (long long)min(max(K, 1), nkc) * sxyc;
+        const int Kc = (K < 1 && lo_phys) ? 1 : ((K > nkc && hi_phys) ? nkc : K);
+        const double* ek = e + (long long)Kc * sxyc;
         __syncthreads();  // the previous plane is read no more
         for (int q = tid; q < kCoarseW * kCoarseH; q += kThreads) {
             const int cx = q % kCoarseW, cy = q / kCoarseW;
@@ -247,11 +256,11 @@ __global__ __launch_bounds__(kThreads) void mg3_prolong_correct_kernel(
                 stp(pl + (long long)(nj + 1) * sx + col, b0.x, b0.y);
                 stp(pu + (long long)(nj + 1) * sx + col, b1.x, b1.y);
             }
-            if (K == 1) {
+            if (K == 1 && lo_phys) {
                 stp(p + ra, a0.x, a0.y);
                 stp(p + rb, b0.x, b0.y);
             }
-            if (K == nkc) {
+            if (K == nkc && hi_phys) {
                 double* const pt = p + (long long)(nk + 1) * sxy;
                 stp(pt + ra, a1.x, a1.y);
                 stp(pt + rb, b1.x, b1.y);
@@ -263,6 +272,18 @@ __global__ __launch_bounds__(kThreads) void mg3_prolong_correct_kernel(
                 mid[y][x] = hi[y][x];
             }
     }
+}
+
+__global__ __launch_bounds__(kThreads) void mg3_prolong_correct_kernel(
+    double* __restrict__ p, const double* __restrict__ e, int nic, int njc, int nkc, long long sx,
+    long long sxy, long long sxc, long long sxyc) {
+    mg3_prolong_correct_body(p, e, nic, njc, nkc, sx, sxy, sxc, sxyc, true, true);
+}
+
+__global__ __launch_bounds__(kThreads) void mg3_prolong_correct_slab_kernel(
+    double* __restrict__ p, const double* __restrict__ e, int nic, int njc, int nkc, long long sx,
+    long long sxy, long long sxc, long long sxyc, int lo_phys, int hi_phys) {
+    mg3_prolong_correct_body(p, e, nic, njc, nkc, sx, sxy, sxc, sxyc, lo_phys != 0, hi_phys != 0);
 }
 
 dim3 mg3_grid(int nic, int njc, int nkc) {
@@ -285,6 +306,14 @@ void launch_mg3_prolong_correct(hipStream_t s, const G3& f, const G3& c, double*
     hipLaunchKernelGGL(mg3_prolong_correct_kernel, mg3_grid(c.I, c.J, c.K),
                        dim3(kMg3TileW, kMg3TileH), 0, s, p, e, c.I, c.J, c.K, f.sx, f.sxy, c.sx,
                        c.sxy);
+}
+
+void launch_mg3_prolong_correct_slab(hipStream_t s, const G3& f, const G3& c, double* p,
+                                     const double* e, long long koff_c, bool lo_phys,
+                                     bool hi_phys) {
+    hipLaunchKernelGGL(mg3_prolong_correct_slab_kernel, mg3_grid(c.I, c.J, c.K),
+                       dim3(kMg3TileW, kMg3TileH), 0, s, p, e + koff_c * c.sxy, c.I, c.J, c.K,
+                       f.sx, f.sxy, c.sx, c.sxy, lo_phys ? 1 : 0, hi_phys ? 1 : 0);
 }
 
 }  // namespace misor

@@ -82,6 +82,36 @@ int allreduce3(misor_grid3* g, double* dev, int n, bool is_max) {
     return MISOR_OK;
 }
 
+// The slabs are equal and contiguous, each whole planes with their ghost
+// columns and rows: over RCCL one in-place all-gather straight in G's rhs, no
+// pack kernel; in process, device-to-device copies from the peers' G between
+// two host barriers, ordered by stream synchronisation like exchange3's.
+int allgather_slabs3(misor_grid3* f, misor_grid3* G, int kc) {
+    if (!dist(f)) return MISOR_OK;
+    const size_t cnt = (size_t)kc * (size_t)G->g.sxy;
+    double* const base = plane_ptr(G, MISOR3_RHS, 1);  // rank 0's slab
+    if (f->local) {
+        LocalGroup<misor_grid3>& L = *f->local;
+        HIPCHK(hipStreamSynchronize(f->stream));
+        L.barrier();  // every rank's restricted slab is final
+        const long long own = base - G->fld[MISOR3_RHS];
+        for (int q = 0; q < f->nranks; ++q) {
+            if (q == f->rank) continue;
+            // rank q's G: the gathered level of the user's grid its level belongs to
+            const misor_grid3* Gq = static_cast<const misor_grid3*>(L.members[q]->peer_gath);
+            HIPCHK(hipMemcpyAsync(base + (size_t)q * cnt,
+                                  Gq->fld[MISOR3_RHS] + own + (size_t)q * cnt,
+                                  cnt * sizeof(double), hipMemcpyDeviceToDevice, f->stream));
+        }
+        HIPCHK(hipStreamSynchronize(f->stream));
+        L.barrier();  // nobody restricts into a slab that is still being copied
+        return MISOR_OK;
+    }
+    NCCLCHK(ncclAllGather(base + (size_t)f->rank * cnt, base, cnt, ncclDouble, f->comm,
+                          f->stream));
+    return MISOR_OK;
+}
+
 // ------------------------------------------------ Cartesian process grid
 // sides in the reference's Direction order: 0 left, 1 right, 2 bottom, 3 top,
 // 4 front, 5 back; side s lies on axis s / 2, its opposite is s ^ 1

@@ -55,7 +55,7 @@ void misor3_destroy(misor_grid3* g) {
     (void)hipFree(g->gbuf);
     for (auto& e : g->ev)
         if (e) (void)hipEventDestroy(e);
-    if (g->comm) ncclCommDestroy(g->comm);
+    if (g->comm && g->own_comm) ncclCommDestroy(g->comm);
     if (g->stream && g->own_stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -75,9 +75,11 @@ int misor3_decompose_cart(int nranks, int rank, const int dims_in[3], int imax, 
 }
 
 // misor3_create (dims == nullptr: slabs) and misor3_create_cart; level_stream:
-// create3_level's grid on that stream, with p, its partner and rhs only
+// create3_level's grid on that stream, with p, its partner and rhs only;
+// parent: create3_level_slab's, on parent's communicator (d->comm_id is not read)
 static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, bool cart,
-                   hipStream_t level_stream = nullptr) {
+                   hipStream_t level_stream = nullptr, misor_grid3* parent = nullptr,
+                   int level = 0) {
     if (!out || !d) return fail(MISOR_EINVAL, "null argument");
     *out = nullptr;
     if (d->imax < 2 || d->jmax < 2 || d->kmax < 2)
@@ -87,7 +89,7 @@ static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, boo
     int kloc = d->kmax, koff = 0;
     misor3_local loc{};
     if (nranks > 1) {
-        if (!d->comm_id) return fail(MISOR_EINVAL, "nranks > 1 needs a comm_id");
+        if (!d->comm_id && !parent) return fail(MISOR_EINVAL, "nranks > 1 needs a comm_id");
         const int rc = cart ? misor3_decompose_cart(nranks, d->rank, dims, d->imax, d->jmax,
                                                     d->kmax, &loc)
                             : misor3_decompose(nranks, d->rank, d->kmax, &kloc, &koff);
@@ -197,13 +199,31 @@ static int create3(misor_grid3** out, const misor3_desc* d, const int* dims, boo
         }
     }
     if (nranks > 1) {
-        char name[MISOR_COMM_ID_BYTES + 1];
-        const LocalJoin joined = join_local_group(d->comm_id, nranks, g->rank, g,
-                                                  4 * (size_t)nranks, g->local, name);
+        // a multigrid level of an in-process group: a group of its own, whose
+        // name every rank derives from the parent's group and the level
+        char derived[MISOR_COMM_ID_BYTES + 1] = {};
+        const void* id_bytes = d->comm_id;
+        if (parent && parent->local) {
+            if (snprintf(derived, sizeof derived, "%s/mg%d", parent->local_name, level) >=
+                MISOR_COMM_ID_BYTES)
+                CF(MISOR_EINVAL, "local group %s: name too long for its multigrid levels",
+                   parent->local_name);
+            id_bytes = derived;
+        }
+        char name[MISOR_COMM_ID_BYTES + 1] = {};
+        const LocalJoin joined =
+            (parent && !parent->local)
+                ? LocalJoin::kNotLocal
+                : join_local_group(id_bytes, nranks, g->rank, g, 4 * (size_t)nranks, g->local,
+                                   name);
         if (joined == LocalJoin::kBadMember)
             CF(MISOR_EINVAL, "local group %s: bad rank/size", name);
         if (joined == LocalJoin::kJoined) {
+            memcpy(g->local_name, name, sizeof name);
             g->local->barrier();  // every member registered before any exchange
+        } else if (parent) {
+            g->comm = parent->comm;
+            g->own_comm = false;
         } else {
             ncclUniqueId id;
             memcpy(&id, d->comm_id, sizeof id);
@@ -229,6 +249,10 @@ int misor3_create_cart(misor_grid3** out, const misor3_desc* d, const int dims[3
 
 int create3_level(misor_grid3** out, const misor3_desc* d, hipStream_t s) {
     return create3(out, d, nullptr, false, s);
+}
+
+int create3_level_slab(misor_grid3** out, const misor3_desc* d, misor_grid3* parent, int level) {
+    return create3(out, d, nullptr, false, parent->stream, parent, level);
 }
 
 extern "C" {

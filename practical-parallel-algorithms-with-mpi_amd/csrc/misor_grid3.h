@@ -2,12 +2,14 @@
 // host units of the 3D path share: misor3d_api.hip (lifecycle, transfers, the
 // Navier-Stokes step, tuning, timing), misor3_comm.hip (halo exchange,
 // all-reduce and gather over RCCL or the in-process transport),
-// misor3_solve.hip (misor3_solve, one function per schedule) and misor3_mg.hip
-// (multigrid).  The decomposition arithmetic is in decomp3.h.
+// misor3_solve.hip (misor3_solve, one function per schedule), misor3_mg.hip
+// (multigrid) and misor3_mg_dist.hip (multigrid on slabs).  The decomposition
+// arithmetic is in decomp3.h.
 // Not part of the public ABI (include/misor.h).
 #pragma once
 
 #include <memory>
+#include <vector>
 
 #include "decomp3.h"  // kHalo: halo planes per side in storage
 #include "local_group.h"
@@ -18,7 +20,25 @@ constexpr int kSlack = 2;         // spare doubles before / after every buffer: 
 constexpr int kBufs = 9;          // the 8 fields + the ping-pong partner of P
 constexpr int kAlt = 8;
 
-struct Mg3Hierarchy;  // the multigrid levels below a grid (misor3_mg.hip)
+struct misor_grid3;
+
+// the multigrid levels below a grid (misor3_mg.hip, misor3_mg_dist.hip)
+struct Mg3Hierarchy {
+    int coarse_cells = -1;
+    std::vector<misor_grid3*> lv;  // lv[0] is the user's grid (not owned)
+    // timing of level 0's transfer kernels (misor3_mg_info.transfer_ms): pair k
+    // is ev[2 * k] (start), ev[2 * k + 1] (stop) around a launch of kind[k]
+    // (0 restriction, 1 prolongation); ev_used pairs are complete
+    std::vector<hipEvent_t> ev;
+    std::vector<int> kind;
+    size_t ev_used = 0;
+    // the decomposed form (misor3_solve_mg_dist): the distributed levels,
+    // dlv[0] the user's grid (not owned), and the gathered level (null where
+    // every level is distributed), whose own hierarchy holds the rest
+    int dist_coarse_cells = -1, dist_ndist = -1;
+    std::vector<misor_grid3*> dlv;
+    misor_grid3* gath = nullptr;
+};
 
 struct misor_grid3 {
     int device = 0;
@@ -37,6 +57,9 @@ struct misor_grid3 {
     int kchunk = 0;            // MISOR3_TUNE_KCHUNK (0: automatic)
     int fold = 1;              // MISOR3_TUNE_FOLD: single rank, loop test inside the sweep
     int resident = -1;         // MISOR3_TUNE_RESIDENT: whole solve in one launch when it fits
+    bool levels_inherit_resident = false;  // the multigrid levels built below this grid take
+                               // its `resident` (the gathered level of misor3_solve_mg_dist);
+                               // false: they keep the default, whatever the grid's own knob
     void* rbar = nullptr;      // its grid-barrier state and partials, uncached memory
     double* rmbox = nullptr;   // its exchange mailboxes (2 x p's layout), uncached memory
     int rhs_ahead = 0;         // MISOR3_TUNE_RHS_AHEAD: fused sweep's rhs loads 1 or 2 steps
@@ -59,6 +82,8 @@ struct misor_grid3 {
     // decomposition
     int nranks = 1, rank = 0, prev = -1, next = -1;
     ncclComm_t comm = nullptr;
+    bool own_comm = true;      // false: a multigrid level on its user's grid's communicator
+    char local_name[MISOR_COMM_ID_BYTES + 1] = {};  // the in-process group's name
     std::shared_ptr<LocalGroup<misor_grid3>> local;  // in-process transport; vals: 4 per rank
     double* gstage = nullptr;     // rank 0: receive staging of misor3_gather (RCCL)
     // Cartesian process grid (misor3_create_cart)
@@ -71,12 +96,21 @@ struct misor_grid3 {
     // multigrid (misor3_mg.hip)
     Mg3Hierarchy* mg = nullptr;
     misor3_mg_info mg_info{};     // the last misor3_solve_mg; transfer times while timing
+    misor_grid3* peer_gath = nullptr;  // on the last distributed level of a decomposed
+                                       // hierarchy: this rank's gathered level, where the
+                                       // in-process all-gather of its peers finds it
 };
 
 // misor3d_api.hip
 // a single-rank grid holding p, its partner and rhs only (no u, v, w, f, g,
 // h), on stream s: a multigrid level
 MISOR_HIDDEN int create3_level(misor_grid3** out, const misor3_desc* d, hipStream_t s);
+// the same decomposed into slabs over parent's ranks (d->nranks, d->rank are
+// parent's), on parent's stream and communicator -- the same ncclComm_t, not
+// owned, or an in-process group of its own named from parent's group and
+// `level`: a distributed multigrid level.  Collective.
+MISOR_HIDDEN int create3_level_slab(misor_grid3** out, const misor3_desc* d, misor_grid3* parent,
+                                    int level);
 
 inline bool dist(const misor_grid3* g) { return g->nranks > 1; }
 // plane kk of buffer b
@@ -105,6 +139,11 @@ MISOR_HIDDEN int allreduce3(misor_grid3* g, double* dev, int n, bool is_max);
 // misor3_gather of a decomposed grid: slabs / Cartesian blocks
 MISOR_HIDDEN int gather_slabs(misor_grid3* g, int field, double* host_global);
 MISOR_HIDDEN int gather_cart(misor_grid3* g, int field, double* host_global);
+// The hand-over of misor3_solve_mg_dist: f is a slab grid, G the whole-domain
+// single-rank grid every rank holds of the level below it, whose kmax is
+// nranks equal slabs of kc planes.  Rank r's planes r kc + 1 .. (r + 1) kc of
+// G's rhs, whole planes with their ghost columns and rows, go to every rank's G.
+MISOR_HIDDEN int allgather_slabs3(misor_grid3* f, misor_grid3* G, int kc);
 
 // misor3_solve.hip
 // planes a workgroup of the fused sweep marches (MISOR3_TUNE_KCHUNK = 0)
@@ -117,3 +156,21 @@ MISOR_HIDDEN int solve3_with(misor_grid3* g, double omega, double eps, int iterm
 
 // misor3_mg.hip
 MISOR_HIDDEN void mg3_free(misor_grid3* g);
+// `who`: the entry point named in the message
+MISOR_HIDDEN int mg3_check_params(const misor_mg_params& q, const char* who);
+MISOR_HIDDEN misor_mg_params mg3_default_params(const misor_grid3* g);
+// nu iterations of the solve without early exit, the carry seeded with 0.0
+MISOR_HIDDEN int mg3_smooth(misor_grid3* g, double omega, int nu, double* res);
+// (re)build the single-rank levels below g for coarse_cells, on g's stream
+MISOR_HIDDEN int mg3_ensure_hierarchy(misor_grid3* g, int coarse_cells);
+// one cycle on level l of g0's single-rank hierarchy
+MISOR_HIDDEN int mg3_cycle(misor_grid3* g0, const misor_mg_params& q, size_t l, double* res);
+// the start (kind 0 / 1) or stop (kind < 0) event around a timed transfer
+// launch of level 0; the times so far into mg_info
+MISOR_HIDDEN int mg3_record_transfer(misor_grid3* g, int kind);
+MISOR_HIDDEN int mg3_collect_transfer_times(misor_grid3* g);
+// misor3_solve_mg past its checks, on a grid that is not decomposed
+MISOR_HIDDEN int mg3_solve_single(misor_grid3* g, const misor_mg_params& q, int* cycles,
+                                  double* res);
+// misor3_mg_dist.hip: the levels of the decomposed form
+MISOR_HIDDEN void mg3_dist_free(Mg3Hierarchy* h);

@@ -398,5 +398,13 @@ void launch_mg3_residual_restrict(hipStream_t s, const G3& f, const G3& c, const
 // p += trilinear interpolation of e, then the ghost copy of p's faces
 void launch_mg3_prolong_correct(hipStream_t s, const G3& f, const G3& c, double* p,
                                 const double* e);
+// the same on a slab of a decomposed grid: c.K coarse planes under the slab's
+// f.K = 2 c.K fine planes, local coarse plane 0 at plane koff_c of e (0: e is a
+// slab's own array with its exchanged halo; the slab's koff / 2: e is the whole
+// domain's array and its neighbouring planes are the real ones); a z side that
+// is not physical reads the plane beyond it and gets no ghost plane written
+void launch_mg3_prolong_correct_slab(hipStream_t s, const G3& f, const G3& c, double* p,
+                                     const double* e, long long koff_c, bool lo_phys,
+                                     bool hi_phys);
 
 }  // namespace misor

@@ -13,7 +13,9 @@
  * entry is chosen automatically: MISOR_DIMS=0x0x0 with 8 ranks is 2x2x2).
  * MISOR_PSOLVE=mg replaces the step's red-black SOR by multigrid V-cycles
  * (misor3_solve_mg, default parameters; single rank only) and prints one line
- * naming the solver; unset or "sor" is the reference's solve.
+ * naming the solver; MISOR_PSOLVE=mgdist is the same on any number of slabs
+ * (misor3_solve_mg_dist, defaults; not with MISOR_DIMS); unset or "sor" is the
+ * reference's solve.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -108,8 +110,8 @@ int main(int argc, char** argv)
     readParameter(&p, argv[1]);
     int dims[3];
     (void)rankDims(dims); /* a malformed MISOR_DIMS ends the program here, before any rank starts */
-    /* MISOR_PSOLVE: a bad value, or mg on more than one rank, ends the program
-     * here, before any rank starts */
+    /* MISOR_PSOLVE: a bad value, mg on more than one rank, or mgdist on a
+     * Cartesian process grid ends the program here, before any rank starts */
     const char* nr = getenv("MISOR_RANKS");
     const char* ws = getenv("WORLD_SIZE");
     const int ranks = nr ? atoi(nr) : (ws ? atoi(ws) : 1);
@@ -118,6 +120,9 @@ int main(int argc, char** argv)
     if (!r || atoi(r) == 0) printParameter3D(&p);
     if (psolve == PSOLVE_MG)
         printf("Pressure solver: geometric multigrid V-cycles (misor3_solve_mg)\n");
+    if (psolve == PSOLVE_MGDIST)
+        printf("Pressure solver: geometric multigrid V-cycles on %d slab%s "
+               "(misor3_solve_mg_dist)\n", ranks > 1 ? ranks : 1, ranks > 1 ? "s" : "");
     fflush(stdout);
     return runRanks(rank_main, &p) ? EXIT_FAILURE : EXIT_SUCCESS;
 }

@@ -25,8 +25,18 @@ int pressureSolver(int ranks)
 {
     const char* v = getenv("MISOR_PSOLVE");
     if (!v || strcmp(v, "sor") == 0) return PSOLVE_SOR;
+    if (strcmp(v, "mgdist") == 0) {
+        int dims[3];
+        if (ranks > 1 && rankDims(dims)) {
+            fprintf(stderr,
+                "MISOR_PSOLVE=mgdist: the decomposed multigrid pressure solve runs on slabs, "
+                "not on a Cartesian process grid (MISOR_DIMS)\n");
+            exit(EXIT_FAILURE);
+        }
+        return PSOLVE_MGDIST;
+    }
     if (strcmp(v, "mg") != 0) {
-        fprintf(stderr, "MISOR_PSOLVE=%s: unknown pressure solver (sor or mg)\n", v);
+        fprintf(stderr, "MISOR_PSOLVE=%s: unknown pressure solver (sor, mg or mgdist)\n", v);
         exit(EXIT_FAILURE);
     }
     if (ranks > 1) {
@@ -126,6 +136,9 @@ void solve(Solver* s)
 {
     if (s->psolve == PSOLVE_MG) /* lastIterations: V-cycles */
         misorCheck(misor3_solve_mg(s->dev, NULL, &s->lastIterations, &s->lastRes), "solve");
+    else if (s->psolve == PSOLVE_MGDIST)
+        misorCheck(misor3_solve_mg_dist(s->dev, NULL, -1, &s->lastIterations, &s->lastRes),
+            "solve");
     else
         misorCheck(misor3_solve(s->dev, &s->lastIterations, &s->lastRes), "solve");
 #ifdef VERBOSE

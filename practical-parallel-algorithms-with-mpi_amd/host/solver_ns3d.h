@@ -37,9 +37,11 @@ typedef struct {
 
 /* MISOR_PSOLVE: unset or "sor" = the reference's red-black SOR (misor3_solve),
  * "mg" = multigrid V-cycles with the default parameters (misor3_solve_mg,
- * single rank only).  pressureSolver() ends the program with a message on any
- * other value, and on "mg" where `ranks` > 1 */
-enum { PSOLVE_SOR = 0, PSOLVE_MG = 1 };
+ * single rank only), "mgdist" = the same on any number of slabs
+ * (misor3_solve_mg_dist).  pressureSolver() ends the program with a message on
+ * any other value, on "mg" where `ranks` > 1 and on "mgdist" with MISOR_DIMS
+ * (a Cartesian process grid) */
+enum { PSOLVE_SOR = 0, PSOLVE_MG = 1, PSOLVE_MGDIST = 2 };
 extern int pressureSolver(int ranks);
 
 extern void initSolver(Solver*, Parameter*);

@@ -90,7 +90,18 @@ class StatsDist(StatsTail):
 
 class MgInfo3(C.Structure):
     _fields_ = [("cycles", C.c_int), ("levels", C.c_int), ("transfer_ms", C.c_double * 2),
-                ("transfers", C.c_longlong)]
+                ("transfers", C.c_longlong), ("dist_levels", C.c_int)]
+
+
+class _MgInfo3Dict(dict):
+    """Grid3.mg_info(): "dist_levels" is an entry where the last solve kept levels
+    distributed and reads as 0 where it did not (misor3_solve_mg, one rank), so
+    that the dict of a single-rank solve is what it was before the field existed"""
+
+    def __missing__(self, key):
+        if key == "dist_levels":
+            return 0
+        raise KeyError(key)
 
 
 class MgParams(C.Structure):
@@ -213,6 +224,10 @@ SIGNATURES = {
                                    C.POINTER(C.c_int), C.c_int]),
     "misor3_solve_mg": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.POINTER(C.c_int), _dp]),
     "misor3_get_mg_info": (C.c_int, [C.c_void_p, C.POINTER(MgInfo3)]),
+    "misor3_solve_mg_dist": (C.c_int, [C.c_void_p, C.POINTER(MgParams), C.c_int,
+                                       C.POINTER(C.c_int), _dp]),
+    "misor3_mg_dist_levels": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -298,6 +313,16 @@ def mg3_levels(imax, jmax, kmax, coarse_cells=512):
     shapes = (C.c_int * (3 * n.value))()
     _check(lib().misor3_mg_levels(imax, jmax, kmax, coarse_cells, C.byref(n), shapes, n.value))
     return [tuple(shapes[3 * k:3 * k + 3]) for k in range(n.value)]
+
+
+def mg3_dist_levels(nranks, imax, jmax, kmax, coarse_cells=512, gather_cells=-1):
+    """(nlevels, ndist): the levels of an imax x jmax x kmax grid and how many of
+    them misor3_solve_mg_dist keeps distributed over nranks slabs
+    (misor3_mg_dist_levels; host-only)"""
+    n, nd = C.c_int(0), C.c_int(0)
+    _check(lib().misor3_mg_dist_levels(nranks, imax, jmax, kmax, coarse_cells, gather_cells,
+                                       C.byref(n), C.byref(nd)))
+    return n.value, nd.value
 
 
 def comm_unique_id() -> bytes:
@@ -748,13 +773,34 @@ class Grid3:
         _check(lib().misor3_solve_mg(self.h, C.byref(q), C.byref(n), C.byref(res)))
         return n.value, res.value
 
+    def solve_mg_dist(self, gather_cells=-1, **params):
+        """multigrid V-cycles on slabs (misor3_solve_mg_dist; collective): (cycles,
+        res).  gather_cells: halved slabs of at most that many cells are gathered
+        (-1: the default); the other keywords as solve_mg's"""
+        q = self.mg_default_params()
+        names = [f[0] for f in MgParams._fields_]
+        for k, v in params.items():
+            if k not in names:
+                raise TypeError("solve_mg_dist: unknown parameter %r (one of %s)" % (k, names))
+            setattr(q, k, v)
+        n, res = C.c_int(0), C.c_double(0.0)
+        _check(lib().misor3_solve_mg_dist(self.h, C.byref(q), gather_cells, C.byref(n),
+                                          C.byref(res)))
+        return n.value, res.value
+
     def mg_info(self):
-        """the last solve_mg: cycles, levels; with timing on the device ms of
-        level 0's two transfer kernels and the launches they cover"""
+        """the last solve_mg / solve_mg_dist: cycles, levels; with timing on the
+        device ms of level 0's two transfer kernels and the launches they cover;
+        ["dist_levels"]: the levels the last solve kept distributed.  Where that is 0
+        (solve_mg, one rank) it is no entry of the dict -- `in`, .get(), .items() and
+        dict() do not see it -- and only indexing gives the 0"""
         s = MgInfo3()
         _check(lib().misor3_get_mg_info(self.h, C.byref(s)))
-        return {"cycles": s.cycles, "levels": s.levels, "transfer_ms": list(s.transfer_ms),
-                "transfers": s.transfers}
+        out = _MgInfo3Dict(cycles=s.cycles, levels=s.levels, transfer_ms=list(s.transfer_ms),
+                           transfers=s.transfers)
+        if s.dist_levels:
+            out["dist_levels"] = s.dist_levels
+        return out
 
     def solve_time(self):
         """(device ms, iterations) of the solves timed since enable_timing"""
